@@ -9,13 +9,17 @@ published epoch time with its tricks enabled).
     python bench.py --gpus 8                      # starts 8 ranks itself (child torchrun)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 \
         --master-port 29500 bench.py --gpus 8 --steps 50 --warmup 10
+    python bench.py --dump-outputs DIR            # + DIR/loss.npy, params.npy (last step)
+
+A plain run sets up, warms up, times ``--steps`` steps and prints the record; ``--full`` is
+where any measurement beyond that belongs (none exists today, so it adds nothing).
 
 One timed step = the full reference training step on synthetic CIFAR-shaped data and
 random-init weights: device-resident batch + GPU augmentation (crop/flip/normalise),
 input mixup, forward + mixup cross-entropy + backward (HIP engine, bf16), bucketed RCCL
 gradient all-reduce overlapped with backward, grad-norm clip (10.0), MADGRAD step
-(the reference's default optimizer for this path, resnet50_test.py:493).  Global batch is
-fixed at 1024 (per-GPU 1024/N, strong scaling).  W warmup steps are
+(the reference's default optimizer for this path, resnet50_test.py:493) at learning rate
+BENCH_LR (small, so that two runs' outputs agree to rounding).  Global batch is fixed at 1024 (per-GPU 1024/N, strong scaling).  W warmup steps are
 untimed; exactly K steps are timed between barrier + device synchronisation on both
 sides; the MAX time over ranks is reported.  Rank 0 prints one JSON line.
 """
@@ -28,6 +32,14 @@ import sys
 import time
 
 BASELINE_IMG_S = 680.0  # ~680 img/s (reference w/ tricks, ~73 s/epoch)
+# Learning rate of the ResNet benchmark's steps.  A step costs the same at any rate, but its
+# outputs do not repeat at the training default (0.02): the engine's fp32 atomic reductions
+# land in a different order every run, MADGRAD's cube root turns that ~1e-3 gradient noise
+# into ~10 % of each update, and at 0.02 the updates outgrow the random-init weights within a
+# few steps (two identical 38-step runs: parameters 0.77 apart in relative L2, loss 2 %).  At
+# 2e-7 the parameters still move (~1e-2 of their norm over 38 steps) and two runs agree to
+# bf16 rounding (38 steps: parameters 1.6e-3, loss 1e-3; 208 steps: 5e-3, 7e-4).
+BENCH_LR = 2e-7
 METRIC = "images/sec (whole node) ResNet-50 bs=1024 DDP at 1/2/4/8 MI355X; epoch time"
 
 
@@ -75,6 +87,14 @@ def parse():
                          "share, optimizer / FSDP shards, bucket plan and graph replay, collectives replaced by "
                          "same-sized local copies (no xGMI time); the record is per-rank, not a scaling point")
     ap.add_argument("--simulate-rank", type=int, default=0)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned and updated as DIR/<name>.npy "
+                         "(fp32: loss, a fixed sample of the parameters); the inputs are "
+                         "seeded, so two builds run with the same arguments can be compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every measurement beyond the headline figure; a plain run times its steps "
+                         "and nothing else (there is no such extra measurement yet: the secondary record "
+                         "fields are by-products of the timed steps)")
     ap.add_argument("--seq-buckets", default="128,256",
                     help="transformer: padded-length buckets (a batch pads to the smallest bucket >= its longest "
                          "sample; the largest bucket must cover the longest sample, so nothing is truncated)")
@@ -129,7 +149,7 @@ def main():
     n = args.simulate_world or int(os.environ.get("WORLD_SIZE", "1"))
     gb = args.global_batch
     assert gb % n == 0, "global batch must divide evenly over ranks"
-    cfg = ResNetConfig(arch=args.arch, bs=gb // n, synthetic=True, eval=False, plot=False,
+    cfg = ResNetConfig(arch=args.arch, bs=gb // n, synthetic=True, eval=False, plot=False, lr=BENCH_LR,
                        distributed=n > 1, ngd=args.ngd, meta_learning=args.meta_learning,
                        optimizer="ngd" if args.ngd else args.optimizer, fsdp=args.fsdp,
                        precision=args.precision, bucket_mb=args.bucket_mb, comm_dtype=args.comm_dtype,
@@ -172,9 +192,10 @@ def main():
     stager = getattr(tr.train_loader, "stager", None)
     w0 = stager.wait_s if stager is not None else 0.0
     t0 = time.perf_counter()
+    loss = None
     for _ in range(args.steps):
         x, y = next(it)
-        tr.train_step(x, y)
+        loss = tr.train_step(x, y)
     host = time.perf_counter() - t0  # host submission time of the K steps (no sync inside)
     waited = (stager.wait_s - w0) if stager is not None else 0.0
     sync()
@@ -201,7 +222,7 @@ def main():
         "data": "synthetic (CIFAR-10-shaped uint8, GPU augmentation), random-init weights",
         "config": {"model": f"{args.arch} (CIFAR stem, 10 classes)", "global_batch": gb, "seq_len": None,
                    "image_size": 32, "parallelism": f"{'fsdp' if args.fsdp else 'dp'}{n}",
-                   "optimizer": "ngd" if args.ngd else args.optimizer, "mixup": "meta" if args.meta_learning else "input",
+                   "optimizer": "ngd" if args.ngd else args.optimizer, "lr": BENCH_LR, "mixup": "meta" if args.meta_learning else "input",
                    "native_kernels": native, "hip_graphs": graphs, "deterministic": args.deterministic},
         "epoch_time_s": round(50000.0 / value, 3),
         "host_ms_per_step": round(host / args.steps * 1e3, 3),
@@ -211,9 +232,33 @@ def main():
     _sharding_fields(tr, rec)
     _dist_fields(rec)
     if tr.rank == 0 or rec.get("simulated"):
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, tr, loss)
         print(json.dumps(rec), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()
+
+
+DUMP_MAX_ELEMS = 8 << 20  # per array (32 MB of fp32): larger ones are sampled
+
+
+def _dump_outputs(path, tr, loss):
+    """``--dump-outputs``: what a caller of the timed path holds after its last step -- the loss
+    ``train_step`` returned, and the parameters it updated in place (this rank's flat buffer or
+    shard; past DUMP_MAX_ELEMS a sorted sample at indices drawn once from a seeded host
+    generator).  The BatchNorm running statistics are left out: the deep layers' running
+    variances magnify parameter differences, and two identical runs were 1.5e-2 apart in them
+    after 208 steps where loss and parameters agreed to bf16 rounding (see BENCH_LR)."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    params = tr.space.data.detach().reshape(-1)
+    if params.numel() > DUMP_MAX_ELEMS:
+        gen = torch.Generator().manual_seed(0)
+        idx = torch.randint(0, params.numel(), (DUMP_MAX_ELEMS,), generator=gen).sort().values
+        params = params[idx.to(params.device)]
+    for name, t in {"loss": loss.detach().reshape(-1), "params": params}.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
 
 
 _COMM0 = None
@@ -335,8 +380,9 @@ def bench_transformer(args):
     t0 = time.perf_counter()
     stager = getattr(tr.train_loader, "stager", None)
     w0 = stager.wait_s if stager is not None else 0.0
+    loss = None
     for _ in range(args.steps):
-        tr.train_step(*next(it))
+        loss = tr.train_step(*next(it))
     host = time.perf_counter() - t0
     waited = (stager.wait_s - w0) if stager is not None else 0.0
     sync()
@@ -363,6 +409,8 @@ def bench_transformer(args):
     _sharding_fields(tr, rec)
     _dist_fields(rec)
     if tr.rank == 0 or rec.get("simulated"):
+        if args.dump_outputs:
+            _dump_outputs(args.dump_outputs, tr, loss)
         print(json.dumps(rec), flush=True)
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -109,6 +109,32 @@ def test_bench_launches_its_own_ranks(tmp_path):
     assert rec["config"]["parallelism"] == "dp2"
 
 
+def test_bench_dump_outputs_repeatable(tmp_path):
+    """``--dump-outputs DIR``: the last timed step's loss and parameters as fp32 .npy
+    files, identical between two runs with the same arguments (seeded inputs; one thread, so the
+    CPU reductions keep their order), and ``--steps`` is the number of timed steps."""
+    import numpy as np
+    env = dict(os.environ, FDT_NATIVE="0", PYTHONPATH=ROOT, OMP_NUM_THREADS="1", MKL_NUM_THREADS="1")
+    env.pop("WORLD_SIZE", None)
+    got = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--arch", "resnet18",
+                            "--global-batch", "8", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / d)],
+                           cwd=tmp_path, env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        rec = _bench_lines(r.stdout)[-1]
+        assert rec["steps"] == 2 and rec["ms_per_step"] > 0
+        assert sorted(os.listdir(tmp_path / d)) == ["loss.npy", "params.npy"]
+        got.append({n: np.load(tmp_path / d / f"{n}.npy") for n in ("loss", "params")})
+    a, b = got
+    from faster_distributed_training_amd.models.resnet import resnet18
+    n_params = sum(p.numel() for p in resnet18(10).parameters())
+    assert a["loss"].shape == (1,) and np.isfinite(a["loss"]).all() and a["params"].shape == (min(n_params, 8 << 20),)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
+    for n in a:
+        assert a[n].dtype == np.float32 and np.array_equal(a[n], b[n]), n
+
+
 def test_bench_refuses_world_size_mismatch(tmp_path):
     env = dict(os.environ, FDT_NATIVE="0", PYTHONPATH=ROOT, WORLD_SIZE="2", RANK="0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1"], cwd=tmp_path,

@@ -8,7 +8,7 @@ from faster_distributed_training_amd.models import resnet as R
 from faster_distributed_training_amd.models import transformer as T
 from faster_distributed_training_amd.ops.conv_bn import FusedConvBN2DFunction, conv_bn_reference
 
-from reference_oracle import load
+from reference_oracle import assert_grads_match, fill_state, golden, golden_json, resnet_batch, schema
 
 
 def test_resnet50_param_counts():
@@ -25,22 +25,20 @@ def test_resnet50_param_counts():
 
 @pytest.mark.parametrize("arch", ["resnet18", "resnet50"])
 def test_resnet_state_dict_matches_reference(arch):
-    ref = load("resnet")
-    a = getattr(R, arch)(10).state_dict()
-    b = getattr(ref, arch)(10).state_dict()
-    assert list(a.keys()) == list(b.keys())
-    for k in a:
-        assert a[k].shape == b[k].shape and a[k].dtype == b[k].dtype, k
+    a = schema(getattr(R, arch)(10).state_dict())
+    b = golden_json("state_dict_schema")[arch]
+    assert [k for k, _, _ in a] == [k for k, _, _ in b]
+    for ea, eb in zip(a, b):
+        assert ea == eb  # key, shape and dtype
 
 
 def test_transformer_state_dict_matches_reference():
-    ref = load("transformer")
     torch.manual_seed(0)
-    a = T.Transformer(4, 1000).state_dict()
-    b = ref.Transformer(4, 1000).state_dict()
-    assert list(a.keys()) == list(b.keys())
-    for k in a:
-        assert a[k].shape == b[k].shape, k
+    a = schema(T.Transformer(4, 1000).state_dict())
+    b = golden_json("state_dict_schema")["transformer_4_1000"]
+    assert [k for k, _, _ in a] == [k for k, _, _ in b]
+    for ea, eb in zip(a, b):
+        assert ea[1] == eb[1], ea[0]
 
 
 def test_transformer_param_count():
@@ -57,15 +55,12 @@ def test_fused_conv_bn_gradcheck():
 
 
 def test_fused_conv_bn_matches_reference_function():
-    ref = load("resnet")
-    torch.manual_seed(0)
-    X = torch.randn(4, 8, 6, 6, dtype=torch.float64, requires_grad=True)
-    W = torch.randn(6, 8, 3, 3, dtype=torch.float64, requires_grad=True)
-    g = torch.randn(4, 6, 6, 6, dtype=torch.float64)
+    rec = golden("fused_conv_bn")  # the reference's FusedConvBN2DFunction on these inputs
+    X, W, g = rec["X"].requires_grad_(), rec["W"].requires_grad_(), rec["g"]
+    assert X.shape == (4, 8, 6, 6) and W.shape == (6, 8, 3, 3) and X.dtype == torch.float64
     out_a = conv_bn_reference(X, W, 1, 1, 1e-3)
     gx_a, gw_a = torch.autograd.grad(out_a, (X, W), g)
-    out_b = ref.FusedConvBN2DFunction.apply(X, W, 1, 1, 1e-3)
-    gx_b, gw_b = torch.autograd.grad(out_b, (X, W), g)
+    out_b, gx_b, gw_b = rec["out"], rec["gx"], rec["gw"]
     assert torch.allclose(out_a, out_b, atol=1e-10)
     assert torch.allclose(gx_a, gx_b, atol=1e-8)
     assert torch.allclose(gw_a, gw_b, atol=1e-8)
@@ -73,21 +68,19 @@ def test_fused_conv_bn_matches_reference_function():
 
 @pytest.mark.parametrize("arch", ["resnet18", "resnet50"])
 def test_resnet_forward_backward_matches_reference(arch):
-    ref = load("resnet")
-    torch.manual_seed(0)
-    mb = getattr(ref, arch)(10).double()
+    """Loss and every parameter's gradient against the reference model's on the same seeded
+    weights (reference_oracle.fill_state) and batch.  The record keeps a fixed sample of each
+    large gradient plus its norm and one dense projection (reference_oracle.grad_record)."""
+    rec = golden(f"{arch}_fwd_bwd")
     ma = getattr(R, arch)(10).double()
-    ma.load_state_dict(mb.state_dict())
+    fill_state(ma.state_dict(), seed=7)
     ma.fast_path = False
-    x = torch.randn(4, 3, 32, 32, dtype=torch.float64)
-    y = torch.randint(0, 10, (4,))
+    x, y = resnet_batch()
     la = F.cross_entropy(ma(x), y)
-    lb = F.cross_entropy(mb(x), y)
-    assert torch.allclose(la, lb, rtol=1e-9, atol=1e-10)
+    assert torch.allclose(la, rec["loss"], rtol=1e-9, atol=1e-10)
     la.backward()
-    lb.backward()
-    for (n, pa), (_, pb) in zip(ma.named_parameters(), mb.named_parameters()):
-        assert ((pa.grad - pb.grad).norm() / pb.grad.norm()).item() < 1e-6, n
+    assert len(rec["norm"]) == len(list(ma.parameters()))
+    assert_grads_match([(n, p.grad) for n, p in ma.named_parameters()], rec, 1e-6)
 
 
 def test_flops_per_image():
@@ -97,22 +90,19 @@ def test_flops_per_image():
 
 
 def test_transformer_pieces_match_reference():
-    ref = load("transformer")
-    torch.manual_seed(0)
-    x = torch.randn(2, 7, 64, dtype=torch.float64)
-    lna, lnb = T.LayerNorm(64).double(), ref.LayerNorm(64).double()
+    rec = golden("transformer_pieces")  # the reference's LayerNorm / Embeddings on these inputs
+    x = rec["x"]
+    assert x.shape == (2, 7, 64) and x.dtype == torch.float64
+    lna = T.LayerNorm(64).double()
     with torch.no_grad():
-        lna.a_2.uniform_()
-        lnb.a_2.copy_(lna.a_2)
-    assert torch.allclose(lna(x), lnb(x), atol=1e-10)
+        lna.a_2.copy_(rec["ln_a_2"])
+    assert torch.allclose(lna(x), rec["ln_out"], atol=1e-10)
     # embeddings (token + position + segment, x sqrt(d))
-    ea, eb = T.Embeddings(64, 50, 16).double(), ref.Embeddings(64, 50, 16).double()
-    ea.load_state_dict(eb.state_dict())
-    ids = torch.randint(0, 50, (2, 7))
-    types = torch.randint(0, 3, (2, 7))
+    ea = T.Embeddings(64, 50, 16).double()
+    ea.load_state_dict({k[len("emb."):]: v for k, v in rec.items() if k.startswith("emb.")})
+    ids, types = rec["ids"], rec["types"]
     idx = torch.arange(16)
-    eb_out = eb(ids, types, idx)
-    assert torch.allclose(ea(ids, types, idx), eb_out.to(torch.float64), atol=1e-6)
+    assert torch.allclose(ea(ids, types, idx), rec["emb_out"].to(torch.float64), atol=1e-6)
 
 
 def test_fused_mlp_bias_grad_fix_and_faithful():
