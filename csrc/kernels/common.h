@@ -55,9 +55,24 @@ template <> __device__ __forceinline__ f16 from_f<f16>(float x) { return __float
 // bf16 bit tricks (exact): bf16 -> f32 is a 16-bit shift.
 __device__ __forceinline__ float bf16_lo(uint32_t u) { return __uint_as_float(u << 16); }
 __device__ __forceinline__ float bf16_hi(uint32_t u) { return __uint_as_float(u & 0xffff0000u); }
+// Two floats -> one packed bf16 pair (round to nearest even, NaN kept): the vector convert is
+// ONE v_cvt_pk_bf16_f32 (two scalar __float2bfloat16 are two of them, each with a dead lane,
+// plus a v_or_b32_sdwa to join the halves).
+typedef float f32x2_t __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
+typedef short i16x2_t __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
-  bf16 a = __float2bfloat16(lo), b = __float2bfloat16(hi);
-  return (uint32_t)(*reinterpret_cast<uint16_t*>(&a)) | ((uint32_t)(*reinterpret_cast<uint16_t*>(&b)) << 16);
+  const f32x2_t f = {lo, hi};
+  return __builtin_bit_cast(uint32_t, __builtin_convertvector(f, bf16x2_t));
+}
+// ReLU of a packed bf16 pair: a signed 16-bit max with 0 (one v_pk_max_i16 for two elements).
+// Negative values, -0 and NaNs with the sign bit set become +0; everything with the sign bit
+// clear -- NaN included, where fmaxf(NaN, 0) gives 0 -- is kept.  Rounding to nearest even
+// never moves a value across zero, so relu-then-round and round-then-relu store the same bits
+// for every non-NaN input.
+__device__ __forceinline__ uint32_t relu_bf16x2(uint32_t u) {
+  const i16x2_t z = {0, 0};
+  return __builtin_bit_cast(uint32_t, __builtin_elementwise_max(__builtin_bit_cast(i16x2_t, u), z));
 }
 
 // ---------------------------------------------------------------- 8-wide vector I/O

@@ -152,6 +152,22 @@ struct ConvArgs {
 };
 
 __device__ __forceinline__ uint32_t pk_bf16(float lo, float hi) { return pack_bf16x2(lo, hi); }
+// fmaf of the staging prologues as an opaque v_fma_f32: once the results feed a pair convert the
+// SLP vectoriser joins two of them into a v_pk_fma_f32, which beside MFMAs costs more than the
+// two scalar instructions it replaces (MI355X: +22 cycles per packed fma).  Same rounding.
+__device__ __forceinline__ float fma1(float a, float b, float c) {
+  float r;
+  asm("v_fma_f32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+  return r;
+}
+// pack, with a ReLU (ACT == kActRelu) applied to the packed pair: one v_pk_max_i16 for two
+// elements instead of two v_max_f32, the same stored bits (common.h relu_bf16x2)
+template <int ACT>
+__device__ __forceinline__ uint32_t pk_act(float lo, float hi) {
+  const uint32_t u = pack_bf16x2(lo, hi);
+  if constexpr (ACT == kActRelu) return relu_bf16x2(u);
+  else return u;
+}
 
 template <int CPR>
 __device__ __forceinline__ int swz(int row) {
@@ -627,6 +643,8 @@ igemm_kernel(const ConvArgs a) {
       *reinterpret_cast<uint4*>(Wl + row * BK + 8 * (cc ^ swz<CPR>(row))) = S.rw[j];
     }
     float sv[8], tv[8], gv[8];
+    // the staging prologues apply a ReLU after packing (pk_act); other activations in fp32
+    constexpr int PACT = ACT == kActRelu ? kActNone : ACT;
     if constexpr (PRO == kProFold) {
       const float4* gp = reinterpret_cast<const float4*>(pst + 2 * a.Cx + S.kci);
       float4 g0 = gp[0], g1 = gp[1];
@@ -650,8 +668,9 @@ igemm_kernel(const ConvArgs a) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) { v[2 * q] = bf16_lo(u[q]); v[2 * q + 1] = bf16_hi(u[q]); }
 #pragma unroll
-        for (int q = 0; q < 8; ++q) v[q] = actf<ACT>(fmaf(v[q], sv[q], tv[q]), a.pro_alpha, inv_alpha);
-        o = make_uint4(pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]), pk_bf16(v[4], v[5]), pk_bf16(v[6], v[7]));
+        for (int q = 0; q < 8; ++q) v[q] = actf<PACT>(fma1(v[q], sv[q], tv[q]), a.pro_alpha, inv_alpha);
+        o = make_uint4(pk_act<ACT>(v[0], v[1]), pk_act<ACT>(v[2], v[3]), pk_act<ACT>(v[4], v[5]),
+                       pk_act<ACT>(v[6], v[7]));
         if (!S.xv[j]) o = make_uint4(0, 0, 0, 0);
       } else if constexpr (PRO == kProJoin) {
         // relu(y*s + t + r*s2 + t2): the previous block's output, rounded to bf16 exactly as
@@ -672,10 +691,12 @@ igemm_kernel(const ConvArgs a) {
         uint32_t mk = 0;
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
-          v[q] = actf<ACT>(fmaf(v[q], sv[q], tv[q]) + fmaf(r[q], s2v[q], t2v[q]), a.pro_alpha, inv_alpha);
+          // (the mask bit comes from the fp32 value: relu(z) > 0 <=> z > 0)
+          v[q] = actf<PACT>(fma1(v[q], sv[q], tv[q]) + fma1(r[q], s2v[q], t2v[q]), a.pro_alpha, inv_alpha);
           mk |= (v[q] > 0.f ? 1u : 0u) << q;
         }
-        o = make_uint4(pk_bf16(v[0], v[1]), pk_bf16(v[2], v[3]), pk_bf16(v[4], v[5]), pk_bf16(v[6], v[7]));
+        o = make_uint4(pk_act<ACT>(v[0], v[1]), pk_act<ACT>(v[2], v[3]), pk_act<ACT>(v[4], v[5]),
+                       pk_act<ACT>(v[6], v[7]));
         if (!S.xv[j]) o = make_uint4(0, 0, 0, 0);
         if (n0 == 0 && S.xv[j]) {
           const long e = ((long)pixb[j] << a.log2Cx) + S.kci;
@@ -693,7 +714,7 @@ igemm_kernel(const ConvArgs a) {
           y[2 * q] = bf16_lo(uy[q]); y[2 * q + 1] = bf16_hi(uy[q]);
         }
 #pragma unroll
-        for (int q = 0; q < 8; ++q) g[q] = fmaf(g[q], gv[q], fmaf(tv[q], y[q], sv[q]));
+        for (int q = 0; q < 8; ++q) g[q] = fma1(g[q], gv[q], fma1(tv[q], y[q], sv[q]));
         o = make_uint4(pk_bf16(g[0], g[1]), pk_bf16(g[2], g[3]), pk_bf16(g[4], g[5]), pk_bf16(g[6], g[7]));
         if (!S.xv[j]) o = make_uint4(0, 0, 0, 0);
       }
