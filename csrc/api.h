@@ -16,6 +16,7 @@ void channel_stats_partial(uint64_t y, uint64_t part, long M, int C, int dt, uin
 void stats_finalize(uint64_t part, int nb, int C, double count, int mode, float eps, float momentum, uint64_t gamma,
                     uint64_t beta, uint64_t run_mean, uint64_t run_var, uint64_t nbt, uint64_t out_s, uint64_t out_t,
                     uint64_t save_mean, uint64_t save_aux, int zero_after, uint64_t stream);
+void bn_frozen_coef(uint64_t table, int units, uint64_t out, uint64_t stream);
 void act_bwd_reduce(uint64_t g, uint64_t x, uint64_t s, uint64_t t, uint64_t gx, uint64_t part, int part_rows, long M,
                     int C, int act, float alpha, int dt, uint64_t stream);
 void reduce_partials(uint64_t part, int nb, int nq, int C, uint64_t out, int zero_after, uint64_t stream);

@@ -178,6 +178,8 @@ __global__ __launch_bounds__(64 * kRedWaves) void stats_finalize_kernel(float* _
   bn_finalize_channel(f, c, S, Q);
 }
 
+__global__ void nbt_increment_kernel(long long* nbt) { nbt[0] += 1; }
+
 // ------------------------------------------------------------------ consumer backward
 // Input transform a = act(x*s + t).  Given g = dL/da:
 //   g_pre = g * act'(x*s+t);  gx = g_pre * s;  part = [sum g_pre*x, sum g_pre]
@@ -784,8 +786,55 @@ void stats_finalize(uint64_t part, int nb, int C, double count, int mode, float 
   FinArgs f{mode, eps, momentum, count, P<const float>(gamma), P<const float>(beta), P<float>(run_mean),
             P<float>(run_var), P<long long>(nbt), P<float>(out_s), P<float>(out_t), P<float>(save_mean),
             P<float>(save_aux)};
+  const bool tracks = (mode == 1 || mode == 3) && run_mean != 0;
+  FDT_CHECK(mode != 3 || (run_mean != 0 && run_var != 0), "mode 3 (tracked FusedConvBN) needs running statistics");
+  FDT_CHECK(!(tracks && momentum < 0.f) || nbt != 0, "cumulative running statistics (momentum < 0) need num_batches_tracked");
   stats_finalize_kernel<<<(C + 63) / 64, 64 * kRedWaves, 0, as_stream(stream)>>>(P<float>(part), part ? nb : 0, C,
                                                                                  zero_after, f);
+  FDT_LAUNCH_CHECK();
+  if (tracks && momentum < 0.f) {
+    // cumulative mode: every channel read the count before this increment (bn_math.h bn_track)
+    nbt_increment_kernel<<<1, 1, 0, as_stream(stream)>>>(P<long long>(nbt));
+    FDT_LAUNCH_CHECK();
+  }
+}
+
+// Frozen-inference coefficients of every unit of a plan in one launch (block u = unit u):
+// table rows of 8 int64 = {run_mean, run_var, gamma, beta, C, offset, kind, eps (double bits)};
+// out[offset .. offset+C) = s, out[offset+C .. offset+2C) = t.
+//   kind 0 (FusedConvBN): s = 1/(sqrt(max(rv, 0)) + eps), t = -rm*s
+//   kind 1 (BatchNorm2d): bn_math.h mode 2 -- s = gamma/sqrt(rv + eps), t = beta - rm*s
+__global__ __launch_bounds__(256) void bn_frozen_coef_kernel(const long long* __restrict__ tab, float* __restrict__ out) {
+  const long long* r = tab + (long)blockIdx.x * 8;
+  const float* rm = reinterpret_cast<const float*>(r[0]);
+  const float* rv = reinterpret_cast<const float*>(r[1]);
+  const float* gamma = reinterpret_cast<const float*>(r[2]);
+  const float* beta = reinterpret_cast<const float*>(r[3]);
+  const int C = (int)r[4];
+  float* o = out + r[5];
+  const int kind = (int)r[6];
+  const double eps = __longlong_as_double(r[7]);
+  for (int c = threadIdx.x; c < C; c += 256) {
+    const double mean = rm[c], var = rv[c];
+    double sc, tt;
+    if (kind == 0) {
+      sc = 1.0 / (sqrt(var > 0.0 ? var : 0.0) + eps);
+      tt = -mean * sc;
+    } else {
+      const double aux = 1.0 / sqrt(var + eps);
+      const double g = gamma ? (double)gamma[c] : 1.0, b = beta ? (double)beta[c] : 0.0;
+      sc = g * aux;
+      tt = b - mean * g * aux;
+    }
+    o[c] = (float)sc;
+    o[C + c] = (float)tt;
+  }
+}
+
+void bn_frozen_coef(uint64_t table, int units, uint64_t out, uint64_t stream) {
+  FDT_CHECK(table != 0 && out != 0 && units >= 0, "bn_frozen_coef: table and output buffer");
+  if (units == 0) return;
+  bn_frozen_coef_kernel<<<units, 256, 0, as_stream(stream)>>>(P<const long long>(table), P<float>(out));
   FDT_LAUNCH_CHECK();
 }
 

@@ -6,7 +6,12 @@
 // mode 1: BatchNorm2d train (biased var + eps, affine, running stats with momentum and the
 //         unbiased var)
 // mode 2: BatchNorm2d eval  (running stats, affine)
-// save_mean[c], save_aux[c]: mode 0 -> sd ; modes 1/2 -> invstd
+// mode 3: FusedConvBN train, tracked: mode 0's outputs, plus running stats like mode 1 (the
+//         unbiased var mode 0 computes)
+// save_mean[c], save_aux[c]: modes 0/3 -> sd ; modes 1/2 -> invstd
+// momentum < 0 (modes 1 / 3): cumulative average, factor 1 / (num_batches_tracked + 1) -- PyTorch's
+// momentum=None; the launcher then increments nbt after the finalize kernel (every channel reads
+// the same count), otherwise the channel-0 thread increments it in place.
 #pragma once
 #include "common.h"
 #include <vector>
@@ -29,19 +34,30 @@ struct FinArgs {
   float* save_aux;
 };
 
+// running statistics of channel c (modes 1 / 3) <- this batch's mean and unbiased variance
+__device__ __forceinline__ void bn_track(const FinArgs& f, int c, double mean, double var_u) {
+  if (f.run_mean) {
+    const double m = f.momentum < 0.f ? 1.0 / (double)(f.nbt[0] + 1) : (double)f.momentum;
+    f.run_mean[c] = (float)((1.0 - m) * f.run_mean[c] + m * mean);
+    f.run_var[c] = (float)((1.0 - m) * f.run_var[c] + m * var_u);
+  }
+  if (f.nbt && c == 0 && f.momentum >= 0.f) f.nbt[0] += 1;
+}
+
 // (s, t) of channel c from its fp64 sums; ``write``: also the unit's outputs (out_s / out_t,
 // saved mean / aux, running statistics, num_batches_tracked) -- exactly one thread per channel
 // may write them
 __device__ __forceinline__ void bn_finalize_st(const FinArgs& f, int c, double S, double Q, float& s_out,
                                                float& t_out, bool write) {
   double sc, tt, mean, aux;
-  if (f.mode == 0) {
+  if (f.mode == 0 || f.mode == 3) {
     mean = S / f.count;
     double var = (Q - S * mean) / (f.count - 1.0);
     if (var < 0.0) var = 0.0;
     aux = sqrt(var);
     sc = 1.0 / (aux + (double)f.eps);
     tt = -mean * sc;
+    if (f.mode == 3 && write) bn_track(f, c, mean, var);
   } else if (f.mode == 1) {
     mean = S / f.count;
     double m2 = Q - S * mean;
@@ -52,11 +68,7 @@ __device__ __forceinline__ void bn_finalize_st(const FinArgs& f, int c, double S
     const double g = f.gamma ? (double)f.gamma[c] : 1.0, b = f.beta ? (double)f.beta[c] : 0.0;
     sc = g * aux;
     tt = b - mean * g * aux;
-    if (write && f.run_mean) {
-      f.run_mean[c] = (float)((1.0 - f.momentum) * f.run_mean[c] + f.momentum * mean);
-      f.run_var[c] = (float)((1.0 - f.momentum) * f.run_var[c] + f.momentum * var_u);
-    }
-    if (write && f.nbt && c == 0) f.nbt[0] += 1;
+    if (write) bn_track(f, c, mean, var_u);
   } else {
     mean = f.run_mean[c];
     aux = 1.0 / sqrt((double)f.run_var[c] + (double)f.eps);

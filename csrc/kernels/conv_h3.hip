@@ -410,7 +410,10 @@ bool launch_h3(int pro, int epi, int act, const ConvArgs& a, int BM, int BN, int
   if (epi == kEpiStats && act == kActNone) { h3_launch_one<BM_, BN_, kEpiStats, kActNone, WM_, WN_, D_, NS_>(a, st); return true; } \
   if (epi == kEpiActBwd && act == kActRelu) { h3_launch_one<BM_, BN_, kEpiActBwd, kActRelu, WM_, WN_, D_, NS_>(a, st); return true; } \
   if (epi == kEpiActBwd && act == kActCelu) { h3_launch_one<BM_, BN_, kEpiActBwd, kActCelu, WM_, WN_, D_, NS_>(a, st); return true; } \
-  if (epi == kEpiStore && act == kActNone) { h3_launch_one<BM_, BN_, kEpiStore, kActNone, WM_, WN_, D_, NS_>(a, st); return true; }
+  if (epi == kEpiStore && act == kActNone) { h3_launch_one<BM_, BN_, kEpiStore, kActNone, WM_, WN_, D_, NS_>(a, st); return true; } \
+  if (epi == kEpiNormAct && act == kActNone) { h3_launch_one<BM_, BN_, kEpiNormAct, kActNone, WM_, WN_, D_, NS_>(a, st); return true; } \
+  if (epi == kEpiNormAct && act == kActRelu) { h3_launch_one<BM_, BN_, kEpiNormAct, kActRelu, WM_, WN_, D_, NS_>(a, st); return true; } \
+  if (epi == kEpiNormAct && act == kActCelu) { h3_launch_one<BM_, BN_, kEpiNormAct, kActCelu, WM_, WN_, D_, NS_>(a, st); return true; }
 #define FDT_H3(BM_, BN_, WM_, WN_)                          \
   if (BM == BM_ && BN == BN_) {                             \
     if (kg == 6) { FDT_H3E(BM_, BN_, WM_, WN_, true, 2) }       \

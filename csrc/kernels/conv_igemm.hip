@@ -97,7 +97,13 @@ static void conv_igemm_impl(uint64_t x, uint64_t x2, uint64_t ps, uint64_t pt, u
   const bool pure = a.ntaps == 1 && dh[0] == 0 && dw[0] == 0 && wt[0] == 0 && S == 1 && Hi == Ho && Wi == Wo;
   hipStream_t st = as_stream(stream);
   if (a.M == 0) return;
-  const int act = (pro == kProAffineAct || pro == kProJoin) ? pro_act : ((epi == kEpiActBwd || epi == kEpiJoinBwd) ? epi_act : 0);
+  if (epi == kEpiNormAct) {
+    FDT_CHECK(pro == kProNone && es != 0 && et != 0, "frozen epilogue: prologue-free, with scale and shift");
+    FDT_CHECK(OS == 1 && oy == 0 && ox == 0 && Hout == Ho && Wout == Wo, "frozen epilogue: dense forward output");
+  }
+  const int act = (pro == kProAffineAct || pro == kProJoin)
+                      ? pro_act
+                      : ((epi == kEpiActBwd || epi == kEpiJoinBwd || epi == kEpiNormAct) ? epi_act : 0);
   if (kg >= 5 && kg <= 8) {  // halo-staged 3x3 stride-1 loop (conv_h3.hip): prologue-free operands, no split-K
     FDT_CHECK(pro == kProNone && a.nsplit == 1, "kg 5-8 (halo 3x3): prologue-free, nsplit 1");
     FDT_CHECK(launch_h3(pro, epi, act, a, BM, BN, kg, st), "kg 5-8 (halo 3x3): unsupported tile / epilogue");
@@ -109,6 +115,7 @@ static void conv_igemm_impl(uint64_t x, uint64_t x2, uint64_t ps, uint64_t pt, u
       launch_cases_fold(pro, epi, act, a, BM, BN, BK, kg, pure, st) ||
       launch_cases_join(pro, epi, act, a, BM, BN, BK, kg, pure, st) ||
       launch_cases_plain(pro, epi, act, a, BM, BN, BK, kg, pure, st) ||
+      launch_cases_infer(pro, epi, act, a, BM, BN, BK, kg, pure, st) ||
       launch_cases_ffn(pro, epi, act, a, BM, BN, BK, kg, pure, st))
     return;
   FDT_CHECK(false, "unsupported (prologue, epilogue) combination");

@@ -41,6 +41,11 @@
 //      EPI_GELU_BWD  the data gradient of the FFN's second linear (g_y W_2 -> dL/dh) finished
 //                  through the GELU-dropout backward: ga = keep*scale*gelu'(a)*acc stored, and
 //                  the column sums of ga = W_1's bias gradient accumulated (fp32 atomics)
+//      EPI_NORMACT  frozen inference: out = act(acc*es[c] + et[c] (+ ex)) in fp32 from the
+//                  accumulator, one rounding to bf16 -- the unit's normalisation (frozen running
+//                  statistics: scale / shift known before the conv runs), its activation and, for
+//                  the last unit of a residual block, the join with the residual `ex`.  No
+//                  statistics, no atomics; the consumer reads final activations (PRO_NONE).
 //      EPI_JOINBWD  accumulate into the existing gradient of a residual-block output AND
 //                  run that block's join backward on it: g_pre = g*act'(out) (ReLU bit
 //                  mask or the stored CELU output), stored in place, plus the per-channel
@@ -90,7 +95,7 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 enum Pro : int { kProNone = 0, kProAffineAct = 1, kProFold = 2, kProJoin = 3 };
 enum Epi : int { kEpiStats = 0, kEpiActBwd = 1, kEpiStore = 2, kEpiAdd = 3, kEpiJoinBwd = 4, kEpiGeluFwd = 5,
-                 kEpiGeluBwd = 6 };
+                 kEpiGeluBwd = 6, kEpiNormAct = 7 };
 
 struct ConvArgs {
   const bf16* x;     // activation operand [Nb][Hi][Wi][Cx]   (PRO_FOLD: the gradient G)
@@ -107,9 +112,10 @@ struct ConvArgs {
   float* part;       // statistics slots [rows][NQ][Cout], fp32 atomics (zeroed by the consumer)
   unsigned slot_mask;  // slot = row block & slot_mask (deterministic mode: no wrap, one writer per slot)
   int det;             // deterministic mode: the split-K reducer sums every split in split order
-  const bf16* ex;    // ACTBWD: producer raw output x (shape of out); JOINBWD: residual-branch y
-  const float* es;   // ACTBWD: producer scale s [Cout]
-  const float* et;   // ACTBWD: producer shift t [Cout]
+  const bf16* ex;    // ACTBWD: producer raw output x (shape of out); JOINBWD: residual-branch y;
+                     // NORMACT: the residual added before the activation, or nullptr
+  const float* es;   // ACTBWD: producer scale s [Cout]; NORMACT: this unit's frozen scale [Cout]
+  const float* et;   // ACTBWD: producer shift t [Cout]; NORMACT: this unit's frozen shift [Cout]
   const uint8_t* jmask;  // JOINBWD: ReLU join bit mask (bit i of byte e/8 = out[e] > 0), or nullptr
   const bf16* jyb;       // JOINBWD: shortcut-branch y (nullptr: identity shortcut)
   const bf16* jout;      // JOINBWD: join output (CELU joins, legacy o-mode; read when jmask and es are nullptr)
@@ -305,7 +311,7 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
   }
   float sbv[8], tbv[8];
   const bool zm = EPI == kEpiJoinBwd && ACT == kActCelu && a.es != nullptr;
-  if (EPI == kEpiActBwd || zm) {
+  if (EPI == kEpiActBwd || EPI == kEpiNormAct || zm) {
     const float4* sp = reinterpret_cast<const float4*>(a.es + c);
     const float4* tp = reinterpret_cast<const float4*>(a.et + c);
     const float4 s0 = sp[0], s1 = sp[1], t0 = tp[0], t1 = tp[1];
@@ -403,6 +409,17 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
             q0[k] = fmaf(gp, ya[k], q0[k]);
             q1[k] += gp;
             if (hb) q2[k] = fmaf(gp, yb[k], q2[k]);
+          }
+          st_out(ro, e * 2u, a.out + e, v, a.wthru);
+        } else if constexpr (EPI == kEpiNormAct) {
+          if (a.ex != nullptr) {
+            float r8[8];
+            Vec8<bf16>::load(a.ex + e, r8);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = actf<ACT>(fmaf(v[k], sv[k], tv[k]) + r8[k], a.epi_alpha, inv_alpha);
+          } else {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[k] = actf<ACT>(fmaf(v[k], sv[k], tv[k]), a.epi_alpha, inv_alpha);
           }
           st_out(ro, e * 2u, a.out + e, v, a.wthru);
         } else if constexpr (EPI == kEpiAdd) {
@@ -1156,6 +1173,8 @@ bool launch_cases_plain(int pro, int epi, int act, const ConvArgs& a, int BM, in
                         hipStream_t st);
 bool launch_cases_ffn(int pro, int epi, int act, const ConvArgs& a, int BM, int BN, int BK, int kg, bool pure,
                       hipStream_t st);
+bool launch_cases_infer(int pro, int epi, int act, const ConvArgs& a, int BM, int BN, int BK, int kg, bool pure,
+                        hipStream_t st);
 // halo-staged 3x3 stride-1 main loop (conv_h3.hip): kg 5 register-staged, kg 6 LDS-DMA (two
 // stages), kg 7 LDS-DMA single stage (two workgroups per CU), kg 8 LDS-DMA two stages, 16 waves
 bool h3_supported(const ConvArgs& a, int BM);

@@ -25,6 +25,7 @@ from . import _native
 
 PRO_NONE, PRO_AFFINE_ACT, PRO_FOLD, PRO_JOIN = 0, 1, 2, 3
 EPI_STATS, EPI_ACTBWD, EPI_STORE, EPI_ADD, EPI_JOINBWD = 0, 1, 2, 3, 4
+EPI_NORMACT = 7  # (5 / 6: the transformer FFN epilogues, ops/ffn.py)
 
 
 def _sp():
@@ -380,7 +381,7 @@ _NOLAZY = ([], [])
 
 
 def conv_fwd(x, wf, shp: ConvShape, s=None, t=None, act=0, alpha=1.0, tile=None, part=None, nsplit=None,
-             fin=None, kg=None, lazy=None):
+             fin=None, kg=None, lazy=None, norm=None, res=None, out_act=None):
     """y = conv(act(x*s+t)) (or conv(x) when s is None and act == 0); returns
     (y [N,Ho,Wo,Cout] bf16, part [STAT_SLOTS,2,Cout] fp32 slots whose row sum is
     (sum y, sum y^2)).  ``part``: a zeroed slot buffer to accumulate into.
@@ -389,12 +390,28 @@ def conv_fwd(x, wf, shp: ConvShape, s=None, t=None, act=0, alpha=1.0, tile=None,
     count) and re-zero the slots.
     ``lazy`` = (ptr list, value list) of the INPUT's statistics left in its producer's slot rows
     (bn_math.h LazyStats): the prologue finalises them itself (s / t unused, written by
-    workgroup 0 for the backward)."""
+    workgroup 0 for the backward).
+    ``norm`` = (s, t) fp32 [Cout]: frozen inference -- the conv's own epilogue stores
+    out_act(y*s + t (+ ``res``)) (EPI_NORMACT; ``res``: a bf16 tensor of the output's shape,
+    ``out_act`` = (act, alpha), default none) and no statistics are taken: no slots, no finalize;
+    returns (out, None).  The input is then final activations (no prologue)."""
     nat = _native.native()
     N, H, W, C = x.shape
     assert C == shp.cxp and x.dtype == torch.bfloat16 and x.is_contiguous()
     Ho, Wo = out_hw(H, W, shp)
     M = N * Ho * Wo
+    frozen = norm is not None
+    if frozen:
+        assert s is None and t is None and act == 0 and lazy is None and part is None and fin is None, \
+            "frozen epilogue: prologue-free, no statistics"
+        es, et = norm
+        for v in (es, et):
+            assert v.dtype == torch.float32 and v.is_contiguous() and v.numel() == shp.cout and v.device == x.device
+        assert res is None or (res.dtype == torch.bfloat16 and res.is_contiguous() and res.device == x.device
+                               and tuple(res.shape) == (N, Ho, Wo, shp.cout))
+        oact, oalpha = out_act if out_act is not None else (0, 1.0)
+    else:
+        assert res is None and out_act is None, "res / out_act belong to the frozen epilogue (norm=)"
     pro = PRO_AFFINE_ACT if (s is not None or act != 0 or lazy is not None) else PRO_NONE
     ent = None
     h3 = None
@@ -412,14 +429,22 @@ def conv_fwd(x, wf, shp: ConvShape, s=None, t=None, act=0, alpha=1.0, tile=None,
     else:
         bm, bn, bk = _tile3(tile, M, shp.cout)
         if nsplit is not None:
-            ent = {"nsplit": nsplit}
+            # (frozen: the layer keeps its tuned K groups and loop form, only the split factor goes)
+            ent = dict(ent or {}, nsplit=nsplit) if frozen else {"nsplit": nsplit}
         ns, slab_p, cnt_p = _splitk_args(ent, M, shp.cout, shp.ntaps * C, bm, bn, bk, x.device)
         kgv = _kg(ent, kg, (bm, bn, bk), ns, shp.ntaps * C, pro)
     _log("fwd", N, H, shp, ent, (bm, bn, bk), ns, kgv)
     y = torch.empty(N, Ho, Wo, shp.cout, device=x.device, dtype=torch.bfloat16)
+    dh, dw, wt = taps_fwd(shp.k, shp.pad)
+    if frozen:
+        nat.conv_igemm(x.data_ptr(), 0, 0, 0, 0, wf.data_ptr(), y.data_ptr(), 0, 0,
+                       _p(res), es.data_ptr(), et.data_ptr(), 0, 0, 0,
+                       N, H, W, C, Ho, Wo, shp.stride, list(dh), list(dw), list(wt), shp.cout, shp.ntaps * shp.cxp,
+                       Ho, Wo, 1, 0, 0, PRO_NONE, 0, 1.0, EPI_NORMACT, int(oact), float(oalpha), bm, bn, bk, ns, slab_p,
+                       cnt_p, _loop_kg(ent, kgv), _sp(), [], [], [])
+        return y, None
     if part is None:
         part = stat_slots(2, shp.cout, x.device, M)
-    dh, dw, wt = taps_fwd(shp.k, shp.pad)
     if pro == PRO_AFFINE_ACT and s is None and lazy is None:
         s = torch.ones(C, device=x.device, dtype=torch.float32)
         t = torch.zeros(C, device=x.device, dtype=torch.float32)

@@ -29,6 +29,8 @@ fp32/fp64 statistics.
 from __future__ import annotations
 
 import os
+import struct
+from collections import OrderedDict
 
 import torch
 import torch.nn as nn
@@ -52,7 +54,7 @@ JOIN_FOLD_MIN_M = int(os.environ.get("FDT_JOIN_FOLD_MIN_M", str(1 << 18)))
 # run the classifier head (average pool + fc, bf16 autocast numerics) as two engine kernels
 # inside the body's graphs instead of eager PyTorch ops (see csrc/kernels/head.hip)
 FUSED_HEAD = os.environ.get("FDT_FUSED_HEAD", "1") != "0"
-MODE_FCBN, MODE_BN_TRAIN, MODE_BN_EVAL = 0, 1, 2
+MODE_FCBN, MODE_BN_TRAIN, MODE_BN_EVAL, MODE_FCBN_TRACK = 0, 1, 2, 3
 BF16 = torch.bfloat16
 # Lazy batch statistics (csrc/kernels/bn_math.h LazyStats): a unit whose statistics fit a few
 # slot rows leaves them there and its CONSUMER (next conv's prologue, the 3x3 materialisation,
@@ -137,12 +139,14 @@ class Unit:
             self.w = conv.conv_weight
             stride, pad = 1, conv.padding
             self.bn = None
+            self.fc = conv  # (tracked running statistics: models.resnet.enable_running_stats)
             self.eps = conv.eps
         else:
             assert isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d)
             self.w = conv.weight
             stride, pad = conv.stride[0], conv.padding[0]
             self.bn = bn
+            self.fc = None
             self.eps = bn.eps
         cout, cin, k, _ = self.w.shape
         self.shp = ci.ConvShape(cin, cout, k, stride, pad)
@@ -151,7 +155,7 @@ class Unit:
 
     def mode(self, training):
         if self.bn is None:
-            return MODE_FCBN
+            return MODE_FCBN_TRACK if (training and self.fc.track_running_stats) else MODE_FCBN
         use_batch = training or not self.bn.track_running_stats
         return MODE_BN_TRAIN if use_batch else MODE_BN_EVAL
 
@@ -223,6 +227,11 @@ class Plan:
                 self.stage_of.append(name)
         self.units = [self.stem] + [u for b in self.blocks for u in (b.units + ([b.shortcut] if b.shortcut else []))]
         self.fsdp = None  # parallel/fsdp.py FullyShardedDP driving the stages as wrap units
+
+    def tracking(self):
+        """The momenta of the FusedConvBN units that update running statistics in train-mode
+        forwards (None: cumulative), in plan order; empty (false) when none does."""
+        return tuple(u.fc.momentum for u in self.units if u.fc is not None and u.fc.track_running_stats)
 
     def pack(self, dev, need_dgrad=True):
         if self.pack_fresh():
@@ -327,6 +336,9 @@ class Plan:
         addresses never move; zeroed at every forward, inside the captured graph)."""
         if not lazy_enabled():
             return {}, None
+        if any(u.fc is not None and u.fc.track_running_stats for u in self.units):
+            raise RuntimeError("FDT_LAZY_STATS=1 (lazy batch statistics) does not update tracked FusedConvBN running "
+                               "statistics: unset it, or do not call enable_running_stats")
         N, H, W = int(shape[0]), int(shape[1]), int(shape[2])
         key = (N, H, W, str(dev))
         cache = self.__dict__.setdefault("_lazy", {})
@@ -430,12 +442,16 @@ def _bn_fin_params(u: Unit, training):
     bn = u.bn
     mode = u.mode(training)
     if bn is not None:
-        mom = bn.momentum if bn.momentum is not None else 0.1
+        mom = bn.momentum if bn.momentum is not None else -1.0  # (None: cumulative average, bn_math.h)
         track = training and bn.track_running_stats
         rm = bn.running_mean if (track or mode == MODE_BN_EVAL) else None
         rv = bn.running_var if (track or mode == MODE_BN_EVAL) else None
         nbt = bn.num_batches_tracked if track else None
         return mode, mom, rm, rv, nbt, bn.weight, bn.bias
+    if mode == MODE_FCBN_TRACK:
+        fc = u.fc
+        mom = fc.momentum if fc.momentum is not None else -1.0
+        return mode, mom, fc.running_mean, fc.running_var, fc.num_batches_tracked, None, None
     return mode, 0.0, None, None, None, None, None
 
 
@@ -560,7 +576,10 @@ def _coef_args(u: Unit, sm, sa, M, training, dev):
                 p.grad = torch.zeros_like(p)
         gg = u.bn.weight.grad if u.bn.weight.requires_grad else None
         gb = u.bn.bias.grad if u.bn.bias.requires_grad else None
-    args = [u.mode(training), float(u.eps), float(M), sm.data_ptr(), sa.data_ptr(), _p(gamma), al.data_ptr(),
+    mode = u.mode(training)
+    if mode == MODE_FCBN_TRACK:
+        mode = MODE_FCBN  # the backward of a tracked unit is the untracked one's (same saved statistics)
+    args = [mode, float(u.eps), float(M), sm.data_ptr(), sa.data_ptr(), _p(gamma), al.data_ptr(),
             be.data_ptr(), _p(gg), _p(gb)]
     return args, (al, be)
 
@@ -1074,6 +1093,8 @@ def resnet_engine_forward(model, x):
     plan.use_graphs = bool(getattr(model, "graph_engine", False)) and (plan.fsdp is None or plan.fsdp.static)
     xin = to_engine_input(x, plan.stem.shp.cxp)
     need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in model.parameters())
+    if not model.training and getattr(model, "eval_stats", "batch") == "running":
+        return resnet_frozen_forward(model, x)  # (refuses gradients and FSDP models itself)
     plan.fc = model.fc
     plan.head_on = head_fusable(model, x, need_grad)
     if need_grad:
@@ -1086,6 +1107,169 @@ def resnet_engine_forward(model, x):
     if plan.head_on:
         return body  # logits of the fused head
     pooled = body.mean(dim=(1, 2), dtype=torch.float32)  # fp32 accumulation, no fp32 copy of the body
+    return model.fc(pooled)
+
+
+# ------------------------------------------------------------------ frozen inference
+# Eval forward with FROZEN statistics (model.eval_stats == "running"): every unit's scale and
+# shift are known before its conv runs, so normalisation, activation and the residual join move
+# into the conv's epilogue (conv_igemm_impl.h EPI_NORMACT) -- one launch per convolution, plus the
+# weight pack, the coefficient kernel (bn_frozen_coef: every unit's (s, t) from the current
+# running statistics, at fixed addresses) and the head.  No statistics, finalize, normalise, join
+# or mask launches; no reduction crosses the rows of the batch.
+FROZEN_GRAPH_SHAPES = 4  # captured input shapes kept per model (oldest dropped first)
+
+
+class _FrozenCoef:
+    """(s, t) of every unit in one flat fp32 buffer + the table bn_frozen_coef fills it from."""
+
+    def __init__(self, plan, dev):
+        rows, off, self.views = [], 0, {}
+        for u in plan.units:
+            C = u.shp.cout
+            if u.bn is None:
+                if not u.fc.track_running_stats:
+                    raise RuntimeError("frozen forward: FusedConvBN without running statistics (enable_running_stats)")
+                src = (u.fc.running_mean, u.fc.running_var, None, None)
+            else:
+                if not u.bn.track_running_stats:
+                    raise RuntimeError("frozen forward: BatchNorm2d without running statistics")
+                src = (u.bn.running_mean, u.bn.running_var, u.bn.weight, u.bn.bias)
+            for t in src:
+                assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C and t.device == dev)
+            eps_bits = struct.unpack("<q", struct.pack("<d", float(u.eps)))[0]
+            rows.append([_p(src[0]), _p(src[1]), _p(src[2]), _p(src[3]), C, off, 0 if u.bn is None else 1, eps_bits])
+            self.views[id(u)] = (off, C)
+            off += 2 * C
+        self.key = _FrozenCoef.key_of(plan, dev)
+        self.table = torch.tensor(rows, dtype=torch.int64, device=dev)
+        self.buf = torch.empty(off, device=dev, dtype=torch.float32)
+        self.n = len(rows)
+
+    @staticmethod
+    def key_of(plan, dev):
+        ptrs = []
+        for u in plan.units:
+            m = u.fc if u.bn is None else u.bn
+            ptrs += [_p(getattr(m, "running_mean", None)), _p(getattr(m, "running_var", None))]
+            if u.bn is not None:
+                ptrs += [_p(u.bn.weight), _p(u.bn.bias)]
+            ptrs.append(_p(u.w))  # (a captured forward packs from, and so bakes in, the weights' storage)
+        fc = getattr(plan, "fc", None)
+        if fc is not None:
+            ptrs += [_p(fc.weight), _p(fc.bias)]
+        return (str(dev), tuple(ptrs))
+
+    def fill(self):
+        _native.native().bn_frozen_coef(self.table.data_ptr(), self.n, self.buf.data_ptr(), _sp())
+
+    def st(self, u):
+        off, C = self.views[id(u)]
+        return self.buf[off:off + C], self.buf[off + C:off + 2 * C]
+
+
+def _frozen_body(plan, xin, coef):
+    """Stem + blocks (+ the fused head) on ``xin`` (engine input layout), frozen statistics."""
+    dev = xin.device
+    plan.pack(dev, need_dgrad=False)
+    coef.fill()
+
+    # deterministic mode: K is never split over workgroups, so every convolution sums K in one
+    # order whatever the batch size -- split-K factors follow the row count, and a batch of one
+    # (split 4-8) otherwise differs from the same image inside a batch of 64 (split 1-4) by single
+    # bf16 roundings that a deep network amplifies (2.4e-2 of the logits of a random-init,
+    # freshly calibrated ResNet-50: profiles/x2/README.md)
+    ns = 1 if _native.deterministic() else None
+
+    def conv(x, u, act, res=None):
+        return ci.conv_fwd(x, u.wf, u.shp, norm=coef.st(u), res=res, out_act=act, nsplit=ns)[0]
+
+    h = conv(xin, plan.stem, plan.stem.act_out)
+    for b in plan.blocks:
+        x_in = h
+        # the shortcut conv stores its normalised output: the residual of the block's last unit
+        r = conv(x_in, b.shortcut, (ACT_NONE, 1.0)) if b.shortcut is not None else x_in
+        for i, u in enumerate(b.units):
+            last = i + 1 == len(b.units)
+            h = conv(h, u, b.join if last else u.act_out, r if last else None)
+    if getattr(plan, "head_on", False):
+        h, _ = head_forward(plan.fc, h)
+    return h
+
+
+class _FrozenGraph:
+    def __init__(self):
+        self.stage = "warm"   # warm (ran eagerly once) -> ready (captured; calls replay)
+        self.pool = self.x = self.h = self.rec = None
+        self.replays = 0
+
+
+def _frozen_coef(plan, dev):
+    coef = plan.__dict__.get("_frozen_coef")
+    if coef is None or coef.key != _FrozenCoef.key_of(plan, dev):
+        coef = plan._frozen_coef = _FrozenCoef(plan, dev)
+        # captured against the old buffers (statistics, affine) or parameters re-pointed since
+        # (model.to, a flat parameter space built later, param.data = ...)
+        plan.__dict__.pop("_frozen_graphs", None)
+    return coef
+
+
+def resnet_frozen_forward(model, x):
+    """Eval forward of ``models.resnet.ResNet`` with frozen (running) statistics; returns logits.
+    With ``model.graph_engine`` the forward of each input shape is captured once (static input /
+    output, a private pool per capture) on its second call and replayed afterwards."""
+    if getattr(model, "_fsdp", None) is not None:
+        raise RuntimeError("eval_stats='running' is not supported on an FSDP-sharded model")
+    if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in model.parameters())):
+        raise RuntimeError("the frozen forward keeps nothing for a backward: run it under torch.no_grad()")
+    plan = getattr(model, "_plan", None)
+    if plan is None:
+        plan = model._plan = Plan(model)
+    plan.fsdp = None
+    xin = to_engine_input(x, plan.stem.shp.cxp)
+    dev = xin.device
+    plan.fc = model.fc
+    plan.head_on = head_fusable(model, x, False)
+    coef = _frozen_coef(plan, dev)
+    st = None
+    if bool(getattr(model, "graph_engine", False)) and os.environ.get("FDT_GRAPHS", "1") != "0":
+        cache = plan.__dict__.setdefault("_frozen_graphs", OrderedDict())
+        key = (tuple(xin.shape), plan.head_on, _native.deterministic())
+        st = cache.get(key)
+        if st is None:
+            st = cache[key] = _FrozenGraph()  # this call: eager warm-up (workspaces, kernel attributes)
+            while len(cache) > FROZEN_GRAPH_SHAPES:
+                cache.popitem(last=False)
+            st = None
+        elif st.stage == "warm":
+            st.pool = torch.cuda.graph_pool_handle()
+            st.x = xin.clone()
+            cur = torch.cuda.current_stream()
+            side = torch.cuda.Stream()
+            side.wait_stream(cur)
+            torch.cuda.synchronize()
+            rec = _graphs.Recorder(st.pool)
+            with torch.cuda.stream(side), _graphs.recording(rec), _graphs.capture_guard():
+                rec.begin()
+                try:
+                    st.h = _frozen_body(plan, st.x, coef)
+                finally:
+                    rec.end()
+            cur.wait_stream(side)
+            st.rec = rec
+            st.stage = "ready"
+    if st is not None:
+        st.x.copy_(xin)
+        st.rec.replay()
+        st.replays += 1
+        body = st.h
+        if plan.head_on:
+            return body.clone()  # (the static output is overwritten by the next replay)
+    else:
+        body = _frozen_body(plan, xin, coef)
+        if plan.head_on:
+            return body
+    pooled = body.mean(dim=(1, 2), dtype=torch.float32)
     return model.fc(pooled)
 
 
@@ -1127,7 +1311,9 @@ class _BodyWithDummy(torch.autograd.Function):
     def forward(ctx, xin, dummy, plan, training):
         st = None
         if graphs_enabled(plan):
-            key = (tuple(xin.shape), bool(training), bool(getattr(plan, "head_on", False)))
+            # (the tracked units' momenta are scalars of the captured finalize launches, and their
+            # sign decides whether the count's increment kernel is captured at all)
+            key = (tuple(xin.shape), bool(training), bool(getattr(plan, "head_on", False)), plan.tracking())
             states = plan.__dict__.setdefault("_graphs", {})
             st = states.get(key)
             if st is None:

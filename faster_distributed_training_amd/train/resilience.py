@@ -147,6 +147,9 @@ def save_last(trainer, epoch: int):
         extra["scheduler"] = trainer.scheduler.state_dict()
     if getattr(trainer, "scaler", None) is not None:
         extra["scaler"] = trainer.scaler.state_dict()
+    stats = trainer.fused_stats() if hasattr(trainer, "fused_stats") else None
+    if stats is not None:
+        extra["fused_stats"] = stats  # (FusedConvBN running statistics: non-persistent buffers)
     meta = getattr(trainer, "meta", None)
     if meta is not None:
         extra["meta"] = {k: v.detach().cpu() for k, v in meta.state_dict().items()}
@@ -177,6 +180,8 @@ def restore_last(trainer) -> bool:
     if ck.get("sharded_optimizer", False) != _sharded(trainer):
         raise RuntimeError(f"{path}: optimizer sharding differs from this run's (--fsdp / sharded NGD)")
     ckpt.load_model_state(trainer.model, ck["net"])
+    if hasattr(trainer, "_load_fused_stats"):
+        trainer._load_fused_stats(ck, path)
     if hasattr(trainer.flat, "refresh_shadow"):
         trainer.flat.refresh_shadow()
     if ck.get("sharded_optimizer", False):

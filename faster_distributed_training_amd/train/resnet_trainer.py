@@ -82,19 +82,49 @@ class ResNetConfig:
     force_sharded: bool = False        # sharded-NGD path even at world size 1 (bench / tests)
     force_ddp: bool = False            # DDP bucket reducer even at world size 1 (bench: the 8-GPU
                                        # path's graph cuts + all-reduce actions on one GPU)
+    eval_stats: str = "batch"          # batch (reference: batch statistics in eval too) | running (track the
+                                       # FusedConvBN running statistics from the first step, evaluate frozen)
+    calibrate_batches: int = 0         # > 0: before each evaluation, re-estimate every unit's running statistics
+                                       # on this many un-mixed, augmented training batches
+    eval_only: bool = False            # with resume: load, (calibrate,) evaluate once; no training
     extra: dict = field(default_factory=dict)
+
+
+def check_eval_config(eval_stats: str, fsdp: bool = False, calibrate_batches: int = 0, eval_only: bool = False,
+                      resume: bool = True):
+    """The one place that refuses inconsistent evaluation switches (the CLIs call it when they
+    parse their arguments, the trainer before it sets anything up)."""
+    if eval_stats not in ("batch", "running"):
+        raise ValueError(f"eval_stats must be 'batch' or 'running', not {eval_stats!r}")
+    if eval_stats == "running" and fsdp:
+        raise ValueError("--eval_stats running is not supported with --fsdp (the frozen forward needs whole, "
+                         "unsharded parameters)")
+    if calibrate_batches < 0:
+        raise ValueError("--calibrate_batches must be >= 0")
+    if calibrate_batches > 0 and eval_stats != "running":
+        # calibration makes every FusedConvBN track: under batch statistics it would change nothing
+        # that is evaluated and silently switch the later training steps to tracked finalizes
+        raise ValueError("--calibrate_batches re-estimates running statistics: it needs --eval_stats running")
+    if eval_only and not resume:
+        raise ValueError("--eval_only evaluates a checkpoint: pass --resume")
 
 
 def build_model(cfg: ResNetConfig, device):
     model = getattr(resnet_models, cfg.arch)(cfg.num_classes)
     model.fast_path = cfg.fast_path
     model.graph_engine = cfg.graphs
-    return model.to(device)
+    model = model.to(device)
+    if cfg.eval_stats == "running":
+        resnet_models.enable_running_stats(model)
+        model.eval_stats = "running"
+    return model
 
 
 class ResNetTrainer:
     def __init__(self, cfg: ResNetConfig):
         self.cfg = cfg
+        # (before any process group is set up)
+        check_eval_config(cfg.eval_stats, cfg.fsdp, cfg.calibrate_batches, cfg.eval_only, cfg.resume)
         self.rank, self.world = 0, 1
         if (cfg.distributed or cfg.fsdp or cfg.force_sharded or cfg.force_ddp
                 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
@@ -113,6 +143,7 @@ class ResNetTrainer:
         if cfg.resume:
             ck = ckpt.load_checkpoint(self.ckpt_path)
             ckpt.load_model_state(self.model, ck["net"])
+            self._load_fused_stats(ck, self.ckpt_path)
         self.meta = None
         if cfg.meta_learning:
             self.meta = MetaMixup(cfg.bs, device=self.device, learnable=cfg.learnable_meta)
@@ -184,6 +215,33 @@ class ResNetTrainer:
     @property
     def last_path(self):
         return resilience.last_path(self.ckpt_path)
+
+    # ------------------------------------------------------------------ running statistics
+    def fused_stats(self):
+        """Checkpoint entry carrying the FusedConvBN running statistics (they are not part of the
+        reference-schema state_dict), or None while the model evaluates with batch statistics."""
+        if self.cfg.eval_stats != "running":
+            return None
+        return resnet_models.running_stats_state(self.model)
+
+    def _load_fused_stats(self, ck, path):
+        if self.cfg.eval_stats != "running":
+            return
+        if "fused_stats" in ck:
+            resnet_models.load_running_stats(self.model, ck["fused_stats"])
+        elif self.cfg.calibrate_batches <= 0:
+            # never score with the initial mean 0 / variance 1
+            raise RuntimeError(f"{path} carries no FusedConvBN running statistics ('fused_stats'): it cannot be "
+                               f"evaluated with --eval_stats running unless --calibrate_batches N re-estimates them")
+
+    @torch.no_grad()
+    def calibrate(self, batches=None):
+        """Re-estimate every unit's running statistics on ``batches`` clean (un-mixed, augmented)
+        training batches."""
+        import itertools
+        n = self.cfg.calibrate_batches if batches is None else batches
+        with self._autocast():
+            resnet_models.calibrate_running_stats(self.model, itertools.islice(iter(self.train_loader), n))
 
     def _lr(self):
         lr = self.cfg.lr
@@ -365,7 +423,9 @@ class ResNetTrainer:
         return rec
 
     @torch.no_grad()
-    def test(self, epoch):
+    def test(self, epoch, save=True):
+        if self.cfg.calibrate_batches > 0:
+            self.calibrate()
         # every rank evaluates with rank 0's running statistics (reference DDP broadcasts
         # buffers at every forward), so the accuracy -- and the collective "new best ->
         # save" decision below -- is the same on every rank
@@ -385,12 +445,21 @@ class ResNetTrainer:
         acc = pdist.broadcast_scalar(acc)  # one decision for all ranks (save_checkpoint is collective)
         self.testing_acc.append(acc)
         print0(f"test epoch {epoch}: acc {acc:.2f}% loss {float(loss_sum) / max(float(total), 1):.4f}")
-        if acc > self.best_acc:
+        if save and acc > self.best_acc:
             prefix = self.cfg.distributed or (not self.cfg.distributed and self.cfg.faithful)
             extra = {"optimizer": self.optimizer.state_dict()} if self.cfg.extra.get("save_optimizer") else None
+            stats = self.fused_stats()
+            if stats is not None:
+                extra = dict(extra or {}, fused_stats=stats)
             ckpt.save_checkpoint(self.ckpt_path, self.model, acc, epoch, module_prefix=prefix, extra=extra)
             self.best_acc = acc
         self.logger.log(epoch=epoch, test_acc=acc)
+        return acc
+
+    def evaluate_only(self):
+        """--eval_only: score the loaded checkpoint once (nothing is trained or saved)."""
+        acc = self.test(self.start_epoch, save=False)
+        print0(f"eval-only: acc {acc:.2f}% (eval_stats {self.cfg.eval_stats}, bs {self.cfg.bs})")
         return acc
 
     def fit(self):
@@ -412,6 +481,10 @@ class ResNetTrainer:
 
 
 def main_ddp(cfg: ResNetConfig):
-    t = ResNetTrainer(cfg).fit()
+    t = ResNetTrainer(cfg)
+    if cfg.eval_only:
+        t.evaluate_only()
+    else:
+        t.fit()
     pdist.cleanup()
     return t

@@ -5,6 +5,7 @@
 #   NGPU=8 bash run_distributed.sh           # both workloads
 #   NGPU=8 bash run_distributed.sh resnet    # one of them
 #   MAX_RESTARTS=3 bash run_distributed.sh resnet --auto_resume
+#   NGPU=8 bash run_distributed.sh resnet --eval_stats running    # track statistics, evaluate frozen
 #       elastic restarts: a failed/killed rank restarts the whole job, which resumes from the
 #       full-state checkpoint of the last completed epoch (checkpoint/*_last.pth)
 set -euo pipefail
@@ -15,7 +16,8 @@ export HSA_ENABLE_IPC_MODE_LEGACY=0 OMP_NUM_THREADS=${OMP_NUM_THREADS:-12}
 RUN="python -m torch.distributed.run --nnodes=1 --nproc_per_node=${NGPU} --master-addr 127.0.0.1 --master_port=${PORT} --max-restarts=${MAX_RESTARTS:-0}"
 WHAT=${1:-all}
 if [[ "$WHAT" == all || "$WHAT" == resnet ]]; then
-  $RUN ./resnet50_test.py --workers 4 --bs $((1024 / NGPU)) --distributed --meta_learning --ngd --lr 0.01 "${@:2}"
+  # (resnet_infer.py: resnet50_test.py's CLI plus --eval_stats / --calibrate_batches / --eval_only)
+  $RUN ./resnet_infer.py --workers 4 --bs $((1024 / NGPU)) --distributed --meta_learning --ngd --lr 0.01 "${@:2}"
 fi
 if [[ "$WHAT" == all || "$WHAT" == transformer ]]; then
   $RUN ./transformer_test.py --workers 4 --batch_size $((256 / NGPU)) --distributed --ngd "${@:2}"

@@ -8,7 +8,7 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-import resnet50_test  # noqa: E402
+import resnet_infer  # noqa: E402  (resnet50_test.py's CLI plus the inference switches)
 
 
 def main(argv=None):
@@ -21,7 +21,7 @@ def main(argv=None):
         argv += ["--gamma", "0.75"]
     if "--ngd" not in argv and "--optimizer" not in argv:
         argv += ["--optimizer", "sgd", "--scheduler", "cosine"]
-    return resnet50_test.main(argv)
+    return resnet_infer.main(argv)
 
 
 if __name__ == "__main__":
