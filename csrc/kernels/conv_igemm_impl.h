@@ -83,10 +83,6 @@
 #include "dropout_math.h"
 #include <vector>
 
-#ifndef FDT_CONV_FRAG_PIPE
-#define FDT_CONV_FRAG_PIPE 0  // 1: +16 VGPRs -- spills 19-125 VGPRs under the occupancy floors (measured, -Rpass-analysis)
-#endif
-
 namespace fdt {
 namespace conv {
 
@@ -148,9 +144,6 @@ struct ConvArgs {
   float* slab;       // split-K partials [tiles][nsplit][TN*TM*4][256] float4
   int* cnt;          // split-K tickets [tiles], zero between launches
   int8_t dh[12], dw[12], wt[12];
-  // lazy batch statistics (bn_math.h): AFFINE_ACT / JOIN take (s, t) -- JOIN's shortcut (s2,
-  // t2) from ls2 -- by finalising the producer's slot rows in the prologue (ps / pt unused)
-  LazyStats ls1, ls2;
   int wthru;              // epilogue output stores write-through (sc1): see st_out
   int dbg;                // cost probes (scripts/conv_probe2.py): bit 0 = skip the statistics atomics
   long Nb_HiWi_Cx_bytes;  // bytes of the activation operand(s)
@@ -747,41 +740,9 @@ igemm_kernel(const ConvArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  // Fragments double-buffered in registers across the tile's 16-deep K steps: step ks+1's LDS
-  // reads issue before step ks's MFMAs (pinned by sched_barrier), so their latency hides behind
-  // MFMAs (FDT_CONV_FRAG_PIPE, off by default: the extra fragment set spills under the occupancy floors).
   auto compute = [&](int buf) {
     const bf16* Wl = gtiles + buf * (WT + XT);
     const bf16* Xl = Wl + WT;
-#if FDT_CONV_FRAG_PIPE
-    bf16x8_t wf[2][TN], xf[2][TM];
-    auto fetch = [&](int ks, int sl) {
-      const int ch = ks * 2 + (lane >> 5);
-#pragma unroll
-      for (int i = 0; i < TN; ++i) {
-        const int row = wn * (BN / 2) + i * 32 + (lane & 31);
-        wf[sl][i] = *reinterpret_cast<const bf16x8_t*>(Wl + row * BK + 8 * (ch ^ swz<CPR>(row)));
-      }
-#pragma unroll
-      for (int j = 0; j < TM; ++j) {
-        const int row = wm * (BM / 2) + j * 32 + (lane & 31);
-        xf[sl][j] = *reinterpret_cast<const bf16x8_t*>(Xl + row * BK + 8 * (ch ^ swz<CPR>(row)));
-      }
-    };
-    fetch(0, 0);
-#pragma unroll
-    for (int ks = 0; ks < BK / 16; ++ks) {
-      const int sl = ks & 1;
-      if (ks + 1 < BK / 16) fetch(ks + 1, sl ^ 1);
-      __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-      for (int i = 0; i < TN; ++i)
-#pragma unroll
-        for (int j = 0; j < TM; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[sl][i], xf[sl][j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#else
 #pragma unroll
     for (int ks = 0; ks < BK / 16; ++ks) {
       const int ch = ks * 2 + (lane >> 5);
@@ -801,7 +762,6 @@ igemm_kernel(const ConvArgs a) {
 #pragma unroll
         for (int j = 0; j < TM; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(wf[i], xf[j], acc[i][j], 0, 0, 0);
     }
-#endif
   };
 
   // this split's K tiles [kb, kb + nk); K group g takes tiles kb + i*KG + g, i < nkk (the
@@ -900,26 +860,17 @@ igemm_kernel(const ConvArgs a) {
   }
   if (grp == 0) {
     if constexpr (HASPRO) {
-      const bool w0 = blockIdx.x == 0;  // the one workgroup that writes a lazy unit's outputs
-      if (PRO != kProFold && a.ls1.base) {
-        lazy_fill<256>(a.ls1, a.Cx, pst, pst + a.Cx, tid, w0);
-      } else {
-        for (int i = tid; i < a.Cx; i += 256) {
-          pst[i] = a.ps[i];
-          pst[a.Cx + i] = a.pt[i];
-        }
+      for (int i = tid; i < a.Cx; i += 256) {
+        pst[i] = a.ps[i];
+        pst[a.Cx + i] = a.pt[i];
       }
       if constexpr (PRO == kProFold) {
         for (int i = tid; i < a.Cx; i += 256) pst[2 * a.Cx + i] = a.pg ? a.pg[i] : 1.f;
       }
       if constexpr (PRO == kProJoin) {
-        if (a.ls2.base) {
-          lazy_fill<256>(a.ls2, a.Cx, pst + 2 * a.Cx, pst + 3 * a.Cx, tid, w0);
-        } else {
-          for (int i = tid; i < a.Cx; i += 256) {
-            pst[2 * a.Cx + i] = a.pg ? a.pg[i] : 1.f;
-            pst[3 * a.Cx + i] = a.pg ? a.pt2[i] : 0.f;
-          }
+        for (int i = tid; i < a.Cx; i += 256) {
+          pst[2 * a.Cx + i] = a.pg ? a.pg[i] : 1.f;
+          pst[3 * a.Cx + i] = a.pg ? a.pt2[i] : 0.f;
         }
       }
     }

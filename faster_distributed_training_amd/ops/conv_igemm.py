@@ -344,26 +344,14 @@ def _finalize_standalone(nat, kind, part, nq, C, fptr, fval):
         nat.stats_bwd_finalize(part.data_ptr(), part.shape[0], nq, C, *a, *b, _sp())
 
 
-# large-M 3x3 convolutions (forward stats epilogue, BN-backward dgrad epilogue) spread their
-# workgroups over this many slot rows: at batch 1024 the 64-row layout's atomic contention costs
-# the 32x32 / 16x16 3x3 convs 4-10 us each in isolation, more than the longer finalize
-# (scripts/conv_probe3.py, profiles/r5/probe3_*.txt) -- but the whole step measured 25.37 ->
-# 25.44 ms (256 rows) / 25.56 (1024), profiles/r5/wide_rows_*.json: off by default (0)
-WIDE_ROWS = int(os.environ.get("FDT_STAT_WIDE_ROWS", "0"))
-WIDE_MIN_M = 1 << 18
-
-
-def slot_rows(M: int | None = None, wide: bool = False) -> int:
+def slot_rows(M: int | None = None) -> int:
     """Statistics slot rows for a producer over M output rows: rows shared by workgroups
     (block index mod rows) -- STAT_SLOTS, or fewer for small M (a conv has at most M/64 row
-    blocks, and fewer rows are less for the finalize to read), or WIDE_ROWS for a ``wide``
-    (3x3) producer over >= WIDE_MIN_M rows -- or in deterministic mode one row per workgroup
-    (the BN-backward kernels cap their grid to the rows)."""
+    blocks, and fewer rows are less for the finalize to read) -- or in deterministic mode one
+    row per workgroup (the BN-backward kernels cap their grid to the rows)."""
     if not _native.deterministic():
         if M is None:
             return STAT_SLOTS
-        if wide and WIDE_ROWS > STAT_SLOTS and M >= WIDE_MIN_M:
-            return WIDE_ROWS
         need = min(STAT_SLOTS, max(1, -(-int(M) // 64)))
         return 1 << (need - 1).bit_length()
     assert M is not None, "deterministic mode sizes the slots by the producer's row count"
@@ -371,26 +359,20 @@ def slot_rows(M: int | None = None, wide: bool = False) -> int:
     return 1 << (need - 1).bit_length()
 
 
-def stat_slots(nq: int, C: int, device, M: int | None = None, wide: bool = False) -> torch.Tensor:
-    """A fresh zeroed statistics-slot buffer [slot_rows(M, wide), nq, C] (the engine instead
+def stat_slots(nq: int, C: int, device, M: int | None = None) -> torch.Tensor:
+    """A fresh zeroed statistics-slot buffer [slot_rows(M), nq, C] (the engine instead
     reuses one persistent workspace that its finalize kernels re-zero)."""
-    return torch.zeros(slot_rows(M, wide), nq, C, device=device, dtype=torch.float32)
-
-
-_NOLAZY = ([], [])
+    return torch.zeros(slot_rows(M), nq, C, device=device, dtype=torch.float32)
 
 
 def conv_fwd(x, wf, shp: ConvShape, s=None, t=None, act=0, alpha=1.0, tile=None, part=None, nsplit=None,
-             fin=None, kg=None, lazy=None, norm=None, res=None, out_act=None):
+             fin=None, kg=None, norm=None, res=None, out_act=None):
     """y = conv(act(x*s+t)) (or conv(x) when s is None and act == 0); returns
     (y [N,Ho,Wo,Cout] bf16, part [STAT_SLOTS,2,Cout] fp32 slots whose row sum is
     (sum y, sum y^2)).  ``part``: a zeroed slot buffer to accumulate into.
     ``fin`` = (fptr, fval): then finalise the batch-norm statistics (stats_finalize
     arguments: gamma beta run_mean run_var nbt s t save_mean save_aux / mode eps momentum
     count) and re-zero the slots.
-    ``lazy`` = (ptr list, value list) of the INPUT's statistics left in its producer's slot rows
-    (bn_math.h LazyStats): the prologue finalises them itself (s / t unused, written by
-    workgroup 0 for the backward).
     ``norm`` = (s, t) fp32 [Cout]: frozen inference -- the conv's own epilogue stores
     out_act(y*s + t (+ ``res``)) (EPI_NORMACT; ``res``: a bf16 tensor of the output's shape,
     ``out_act`` = (act, alpha), default none) and no statistics are taken: no slots, no finalize;
@@ -402,7 +384,7 @@ def conv_fwd(x, wf, shp: ConvShape, s=None, t=None, act=0, alpha=1.0, tile=None,
     M = N * Ho * Wo
     frozen = norm is not None
     if frozen:
-        assert s is None and t is None and act == 0 and lazy is None and part is None and fin is None, \
+        assert s is None and t is None and act == 0 and part is None and fin is None, \
             "frozen epilogue: prologue-free, no statistics"
         es, et = norm
         for v in (es, et):
@@ -412,7 +394,7 @@ def conv_fwd(x, wf, shp: ConvShape, s=None, t=None, act=0, alpha=1.0, tile=None,
         oact, oalpha = out_act if out_act is not None else (0, 1.0)
     else:
         assert res is None and out_act is None, "res / out_act belong to the frozen epilogue (norm=)"
-    pro = PRO_AFFINE_ACT if (s is not None or act != 0 or lazy is not None) else PRO_NONE
+    pro = PRO_AFFINE_ACT if (s is not None or act != 0) else PRO_NONE
     ent = None
     h3 = None
     if kg in H3_KGS:
@@ -441,40 +423,38 @@ def conv_fwd(x, wf, shp: ConvShape, s=None, t=None, act=0, alpha=1.0, tile=None,
                        _p(res), es.data_ptr(), et.data_ptr(), 0, 0, 0,
                        N, H, W, C, Ho, Wo, shp.stride, list(dh), list(dw), list(wt), shp.cout, shp.ntaps * shp.cxp,
                        Ho, Wo, 1, 0, 0, PRO_NONE, 0, 1.0, EPI_NORMACT, int(oact), float(oalpha), bm, bn, bk, ns, slab_p,
-                       cnt_p, _loop_kg(ent, kgv), _sp(), [], [], [])
+                       cnt_p, _loop_kg(ent, kgv), _sp(), [])
         return y, None
     if part is None:
         part = stat_slots(2, shp.cout, x.device, M)
-    if pro == PRO_AFFINE_ACT and s is None and lazy is None:
+    if pro == PRO_AFFINE_ACT and s is None:
         s = torch.ones(C, device=x.device, dtype=torch.float32)
         t = torch.zeros(C, device=x.device, dtype=torch.float32)
-    lz = lazy if lazy is not None else _NOLAZY
     nat.conv_igemm(x.data_ptr(), 0, _p(s), _p(t), 0, wf.data_ptr(), y.data_ptr(), part.data_ptr(), part.shape[0],
                    0, 0, 0, 0, 0, 0,
                    N, H, W, C, Ho, Wo, shp.stride, list(dh), list(dw), list(wt), shp.cout, shp.ntaps * shp.cxp,
                    Ho, Wo, 1, 0, 0, pro, int(act), float(alpha), EPI_STATS, 0, 1.0, bm, bn, bk, ns, slab_p, cnt_p,
-                   _loop_kg(ent, kgv), _sp(), lz[0], lz[1], [])
+                   _loop_kg(ent, kgv), _sp(), [])
     if fin is not None:
         _finalize_standalone(nat, 1, part, 2, shp.cout, fin[0], fin[1])
     return y, part
 
 
 def conv_fwd_join(y, r, s, t, s2, t2, wf, shp: ConvShape, jout, jmask=None, tile=None, part=None, nsplit=None,
-                  fin=None, kg=None, lazy=None, lazy2=None):
+                  fin=None, kg=None):
     """1x1 stride-1 forward conv of a residual block's joined output, computed on the fly:
     the operand is a = relu(y*s + t + (r*s2 + t2 if s2 is not None else r)) -- the previous
     block's join (BN'd residual branch y + BN'd or identity shortcut r).  ``jout`` receives
     ``a`` (bf16, the block output the next join and the backward read) and ``jmask`` its
     ReLU bit mask (None: not stored), written once by the first output-channel tile; the
     standalone join kernel and this conv's re-read of ``a`` become one pass.  Returns
-    (conv output, statistics slots) like ``conv_fwd``.  ``lazy`` / ``lazy2``: the branches'
-    statistics left in their producers' slot rows (see ``conv_fwd``; s / t and s2 / t2 unused)."""
+    (conv output, statistics slots) like ``conv_fwd``."""
     nat = _native.native()
     N, H, W, C = y.shape
     assert shp.k == 1 and shp.stride == 1 and shp.pad == 0 and C == shp.cin == shp.cxp
     for tt in (y, r, jout):
         assert tt.dtype == torch.bfloat16 and tt.is_contiguous() and tuple(tt.shape) == (N, H, W, C)
-    assert (s2 is None) == (t2 is None) and (lazy2 is None or lazy is not None)
+    assert (s2 is None) == (t2 is None)
     assert jmask is None or (jmask.dtype == torch.uint8 and jmask.numel() * 8 >= y.numel())
     M = N * H * W
     ent = None
@@ -490,12 +470,9 @@ def conv_fwd_join(y, r, s, t, s2, t2, wf, shp: ConvShape, jout, jmask=None, tile
     out = torch.empty(N, H, W, shp.cout, device=y.device, dtype=torch.bfloat16)
     if part is None:
         part = stat_slots(2, shp.cout, y.device, M)
-    l1 = lazy if lazy is not None else _NOLAZY
-    l2 = lazy2 if lazy2 is not None else _NOLAZY
     nat.conv_igemm_join(y.data_ptr(), r.data_ptr(), _p(s), _p(t), _p(s2), _p(t2), wf.data_ptr(),
                         out.data_ptr(), part.data_ptr(), part.shape[0], jout.data_ptr(), _p(jmask), N, H, W, C,
-                        shp.cout, shp.ntaps * shp.cxp, bm, bn, bk, ns, slab_p, cnt_p, _loop_kg(ent, kgv), _sp(),
-                        l1[0], l1[1], l2[0], l2[1])
+                        shp.cout, shp.ntaps * shp.cxp, bm, bn, bk, ns, slab_p, cnt_p, _loop_kg(ent, kgv), _sp())
     if fin is not None:
         _finalize_standalone(nat, 1, part, 2, shp.cout, fin[0], fin[1])
     return out, part
@@ -583,7 +560,7 @@ def conv_dgrad(g, y, al, be, wd, shp: ConvShape, x_shape, epi=EPI_STORE, out=Non
                        _p(jmask), _p(jyb), _p(jout), N, Hy, Wy, Cy, Ha, Wa, 1,
                        list(dh), list(dw), list(wt), shp.cin, shp.ntaps * shp.cout, Hx, Wx, shp.stride, py, px,
                        pro, 0, 1.0, epi, int(act), float(alpha), bm, bn, bk, ns, slab_p, cnt_p, _loop_kg(ent, kgv),
-                       _sp(), [], [], [_p(v) for v in jz] if jz is not None else [])
+                       _sp(), [_p(v) for v in jz] if jz is not None else [])
     if coef is not None:
         _finalize_standalone(nat, 2, part, 3 if epi == EPI_JOINBWD else 2, shp.cin, coef[0], coef[1])
     return out, (part if epi in (EPI_ACTBWD, EPI_JOINBWD) else None)

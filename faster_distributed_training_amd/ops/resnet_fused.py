@@ -56,23 +56,12 @@ JOIN_FOLD_MIN_M = int(os.environ.get("FDT_JOIN_FOLD_MIN_M", str(1 << 18)))
 FUSED_HEAD = os.environ.get("FDT_FUSED_HEAD", "1") != "0"
 MODE_FCBN, MODE_BN_TRAIN, MODE_BN_EVAL, MODE_FCBN_TRACK = 0, 1, 2, 3
 BF16 = torch.bfloat16
-# Lazy batch statistics (csrc/kernels/bn_math.h LazyStats): a unit whose statistics fit a few
-# slot rows leaves them there and its CONSUMER (next conv's prologue, the 3x3 materialisation,
-# the residual join) finalises them while staging its input -- no standalone finalize launch
-# (and its kernel boundary) between producer and consumer.  Budget: slot rows x channels a
-# consumer workgroup reduces (rows = one per 32 producer row blocks, so <= 32 fp32 atomic adders
-# per slot address, the full-rate regime of the memory-side atomics).
-LAZY_STATS = os.environ.get("FDT_LAZY_STATS", "0") == "1"
-LAZY_BUDGET = int(os.environ.get("FDT_LAZY_BUDGET", "2048"))
-# which consumers finalise lazily: "elementwise" (the 3x3 materialisation / stem pass and the
-# residual join pass) or "all" (also the conv prologues: AFFINE_ACT / JOIN)
-LAZY_SCOPE = os.environ.get("FDT_LAZY_SCOPE", "elementwise")
 
 # Parameters whose gradient the engine writes itself call these hooks (the DDP reducer
 # registers here in addition to autograd's post-accumulate-grad hooks).  A "deferrable"
 # hook (the reducer's) takes ``defer=True`` and returns its GPU action (a bucket
-# all-reduce) instead of launching it, so the engine can first join its weight-gradient
-# stream (below) -- and, while capturing, cut the HIP graph there.
+# all-reduce) instead of launching it, so that, while capturing, the HIP graph can be cut
+# there.
 _GRAD_READY_HOOKS: dict[int, list] = {}
 
 
@@ -106,11 +95,6 @@ def grad_ready(param):
             fn(param)
     if not acts:
         return
-    br = _ACTIVE_BRANCH
-    if br is not None and torch.cuda.current_stream() == br.main:
-        # a bucket completed by a gradient the main stream wrote (BN parameters): its other
-        # members may be weight gradients still running on the weight-gradient branch
-        br.join(keep=True)
     if rec is not None:
         rec.cut(acts)
     else:
@@ -329,60 +313,6 @@ class Plan:
     # ---- FSDP: units are gathered stage by stage, so weights are packed per stage (the
     # forward layout before the stage's forward, the dgrad layout before its backward) and
     # the packed copies are released with the gathered parameters
-    # ---- lazy statistics: which units leave their statistics to the consumer, and where
-    def lazy_layout(self, shape, dev):
-        """{id(unit): (offset, rows)} of the lazy units for an input of ``shape`` (NHWC) and the
-        zeroed slot arena they accumulate into (one arena per input shape: a captured graph's
-        addresses never move; zeroed at every forward, inside the captured graph)."""
-        if not lazy_enabled():
-            return {}, None
-        if any(u.fc is not None and u.fc.track_running_stats for u in self.units):
-            raise RuntimeError("FDT_LAZY_STATS=1 (lazy batch statistics) does not update tracked FusedConvBN running "
-                               "statistics: unset it, or do not call enable_running_stats")
-        N, H, W = int(shape[0]), int(shape[1]), int(shape[2])
-        key = (N, H, W, str(dev))
-        cache = self.__dict__.setdefault("_lazy", {})
-        ent = cache.get(key)
-        if ent is None:
-            offs, tot = {}, 0
-
-            def add(u, h, w, conv_consumer=False):
-                nonlocal tot
-                ho, wo = ci.out_hw(h, w, u.shp)
-                r = lazy_rows(N * ho * wo)
-                # FusedConvBN units (mode 0) only: nn.BatchNorm2d units keep the standalone finalize
-                # (running statistics, affine)
-                if (u.bn is None and r * u.shp.cout <= LAZY_BUDGET and N * ho * wo > 1
-                        and (LAZY_SCOPE == "all" or not conv_consumer)):
-                    offs[id(u)] = (tot, r)
-                    tot += (r * 2 + 4) * u.shp.cout  # slots | s | t | mean | sd
-                return ho, wo
-
-            h, w = add(self.stem, H, W)
-            for bi, b in enumerate(self.blocks):
-                hin, win = h, w
-                nxt = self.blocks[bi + 1] if bi + 1 < len(self.blocks) else None
-                ho_, wo_ = h, w
-                for u in b.units:
-                    ho_, wo_ = ci.out_hw(ho_, wo_, u.shp)
-                folded = (nxt is not None and b.join[0] == ACT_RELU
-                          and _join_fold_tile(nxt, (N, ho_, wo_)) is not None)
-                for i, u in enumerate(b.units):
-                    if i + 1 < len(b.units):
-                        v = b.units[i + 1]  # consumer: a conv prologue unless a materialised 3x3
-                        cc = not (MATERIALIZE_3X3 and v.shp.k > 1)
-                    else:
-                        cc = folded  # the join: a pass, or the next block's first conv (PRO_JOIN)
-                    h, w = add(u, h, w, cc)
-                if b.shortcut is not None:
-                    add(b.shortcut, hin, win, folded)
-            arena = torch.zeros(max(tot, 1), device=dev, dtype=torch.float32)
-            ent = cache[key] = (offs, arena, tot)
-        offs, arena, tot = ent
-        if tot:
-            arena[:tot].zero_()
-        return offs, arena
-
     def stage_units(self, name):
         if name == "conv1":
             return [self.stem]
@@ -420,15 +350,14 @@ def _restore(t):
 _SLOTS: dict = {}
 
 
-def slots(nq, C, dev, M, wide=False):
+def slots(nq, C, dev, M):
     """The persistent statistics-slot workspace viewed as [rows, nq, C] for a producer over
-    M output rows (rows = 64, more for a large-M 3x3 conv (``wide``), or one per workgroup in
-    deterministic mode: ci.slot_rows).
+    M output rows (rows = 64, or one per workgroup in deterministic mode: ci.slot_rows).
     Producers (conv epilogues, BN-backward reductions) add into it with fp32 atomics; the
     consuming finalize / reduce kernel sums it in fp64 and re-zeroes it, so the next
     producer needs no memset.  One workspace suffices: every producer is consumed before
     the next one (and a view only ever covers rows its finalize re-zeroes)."""
-    rows = ci.slot_rows(M, wide)
+    rows = ci.slot_rows(M)
     n = max(ci.STAT_SLOTS * 3 * 2048, rows * nq * C)
     ws = _SLOTS.get(dev)
     if ws is None or ws.numel() < n:
@@ -455,62 +384,28 @@ def _bn_fin_params(u: Unit, training):
     return mode, 0.0, None, None, None, None, None
 
 
-def lazy_enabled() -> bool:
-    return LAZY_STATS and not _native.deterministic() and hasattr(_native.native(), "act_affine_lazy")
-
-
-def lazy_rows(M: int) -> int:
-    """Slot rows of a lazy producer over M output rows: one per 32 row blocks of the smallest
-    (64-row) tile, a power of two <= 64."""
-    nb = -(-int(M) // 64)
-    r = 1
-    while r * 32 < nb and r < 64:
-        r *= 2
-    return r
-
-
-def _out_stats(u: Unit, M, training, dev, lay):
-    """(statistics outputs (s, t, save_mean, save_aux), slot view, standalone-finalize args
-    or None, lazy descriptor or None) of one unit's conv.  A lazy unit's outputs are views of
-    its arena region (bn_math.h LazyStats layout), written by its consumer."""
-    ent = lay[0].get(id(u)) if lay is not None else None
-    if ent is None:
-        st, fin = _fin_args(u, M, training, dev)
-        return st, slots(2, u.shp.cout, dev, M, u.shp.k > 1), fin, None
-    off, rows = ent
-    C = u.shp.cout
-    reg = lay[1][off:off + (rows * 2 + 4) * C]
-    part = reg[:rows * 2 * C].view(rows, 2, C)
-    outs = reg[rows * 2 * C:].view(4, C)
-    st = (outs[0], outs[1], outs[2], outs[3])
-    return st, part, None, ([reg.data_ptr()], [float(rows), float(u.eps), float(M)])
-
-
-def conv_bn_fwd(x, u: Unit, s, t, act, training, dev, lazy_in=None, lay=None):
-    """One unit's conv + batch statistics -> (y, (s, t, save_mean, save_aux), M, lazy).
-    ``lazy_in``: the input's statistics are finalised in this conv's prologue; ``lazy`` (not
-    None): this unit's own are left in the slot arena for its consumer (``Plan.lazy_layout``),
-    otherwise a standalone finalize follows the conv."""
+def conv_bn_fwd(x, u: Unit, s, t, act, training, dev):
+    """One unit's conv + batch statistics -> (y, (s, t, save_mean, save_aux), M)."""
     Ho, Wo = ci.out_hw(x.shape[1], x.shape[2], u.shp)
     M = x.shape[0] * Ho * Wo
-    st, part, fin, lz = _out_stats(u, M, training, dev, lay)
+    st, fin = _fin_args(u, M, training, dev)
     y, _ = ci.conv_fwd(x, u.wf, u.shp, s, t, act[0] if act else 0, act[1] if act else 1.0,
-                       part=part, fin=fin, lazy=lazy_in)
-    return y, st, M, lz
+                       part=slots(2, u.shp.cout, dev, M), fin=fin)
+    return y, st, M
 
 
-def conv_bn_fwd_join(pj, u: Unit, training, dev, lay=None, tile=None):
+def conv_bn_fwd_join(pj, u: Unit, training, dev, tile=None):
     """``conv_bn_fwd`` of a block's first (1x1) unit whose input is the PREVIOUS block's
     join, computed in the conv's operand staging (ci.conv_fwd_join); the join output (this
     block's x_in) and its ReLU mask are stored on the way.  pj = (y, s, t, r, s2, t2, out,
-    mask, lazy, lazy2); ``tile``: _join_fold_tile's choice (None / "tuned": the tuned table)."""
-    y, s, t, r, s2, t2, out, mask, lz1, lz2 = pj
+    mask); ``tile``: _join_fold_tile's choice (None / "tuned": the tuned table)."""
+    y, s, t, r, s2, t2, out, mask = pj
     M = y.numel() // y.shape[-1]
-    st, part, fin, lz = _out_stats(u, M, training, dev, lay)
+    st, fin = _fin_args(u, M, training, dev)
     tile = None if tile == "tuned" else tile
-    yo, _ = ci.conv_fwd_join(y, r, s, t, s2, t2, u.wf, u.shp, out, mask, part=part, fin=fin, tile=tile, lazy=lz1,
-                             lazy2=lz2)
-    return yo, st, M, lz
+    yo, _ = ci.conv_fwd_join(y, r, s, t, s2, t2, u.wf, u.shp, out, mask, part=slots(2, u.shp.cout, dev, M), fin=fin,
+                             tile=tile)
+    return yo, st, M
 
 
 def _join_fold_tile(b_next, shape):
@@ -630,102 +525,6 @@ def _rows(t):
     return t.numel() // t.shape[-1]
 
 
-# weight gradients on a second stream (a parallel branch of the captured backward graph): they
-# depend only on operands the dgrad chain has already produced, and nothing on the chain reads
-# them until the optimizer, so each one can run beside the next units' dgrad -> BN-backward
-# finalize -> fold chain.  Measured SLOWER on MI355X: batch 128 5.37 -> 5.96-5.99 ms, batch 1024
-# 24.93 -> 25.32 ms (profiles/r5/wgrad_branch_*.json) -- the ~50 cross-stream fork / join
-# dependencies per replayed backward cost more than the overlap returns, and the concurrent
-# weight-gradient grids take CUs from the critical-path chain.  Opt-in (FDT_WGRAD_BRANCH=1).
-WGRAD_BRANCH = os.environ.get("FDT_WGRAD_BRANCH", "0") == "1"
-WGRAD_BRANCH_KEEP = 8 << 30  # bytes of branch operands held before a full join
-
-
-class _WgradBranch:
-    """The weight-gradient branch of one backward.  Hazards: (1) every operand a branch kernel
-    reads stays referenced until the main stream has joined the branch, so the allocator cannot
-    hand its memory to a main-stream tensor while the branch still reads it; (2) the one
-    in-place overwrite of a branch operand -- an identity block's g_pre, accumulated into by
-    its first unit's dgrad (g_x aliases g_pre) -- waits for the event recorded after the wgrad
-    that reads it (``guard`` / ``wait``)."""
-
-    _streams: dict = {}
-
-    def __init__(self, dev):
-        s = _WgradBranch._streams.get(dev)
-        if s is None:
-            s = _WgradBranch._streams[dev] = torch.cuda.Stream(device=dev)
-        self.s = s
-        self.main = torch.cuda.current_stream(dev)
-        self.keep = []
-        self.kept = 0
-        self.event = None
-        self._seg = None
-
-    @staticmethod
-    def make(dev):
-        if not (WGRAD_BRANCH and dev.type == "cuda"):
-            return None
-        return _WgradBranch(dev)
-
-    def run(self, u, g, y, al, be, x, xs, xt, act, gs=None, guard=False):
-        rec = _graphs.active()
-        if rec is not None and (rec, len(rec.segments)) != self._seg:
-            # a graph segment may end at a hook's cut: the branch forked in it rejoins first
-            self._seg = (rec, len(rec.segments))
-            rec.joiners.append(lambda b=self.s: torch.cuda.current_stream().wait_stream(b))
-        self.s.wait_stream(self.main)
-        key = self._key()
-        with torch.cuda.stream(self.s):
-            wgrad_into(u, g, y, al, be, x, xs, xt, act, gs=gs)
-            # (a gradient hook inside may have cut the graph: the ended segment joined this
-            # branch, which is no longer part of the capture -- nothing to record then)
-            if guard and self._key() == key:
-                ev = torch.cuda.Event()
-                ev.record(self.s)
-                self.event = (ev, key)
-        ops = [t for t in (g, y, al, be, x, xs, xt, gs) if isinstance(t, torch.Tensor)]
-        self.keep.append(ops)
-        self.kept += sum(t.numel() * t.element_size() for t in ops)
-        if self.kept > WGRAD_BRANCH_KEEP:
-            self.join()
-
-    @staticmethod
-    def _key():
-        rec = _graphs.active()
-        return None if rec is None else (rec, len(rec.segments))
-
-    def _stale(self):
-        """Under a graph recording whose segment ended since the branch last forked: the
-        segment end already joined the branch (its joiner), and an event from the ended
-        capture would be a dependency on uncaptured work."""
-        rec = _graphs.active()
-        return rec is not None and (rec, len(rec.segments)) != self._seg
-
-    def wait(self):
-        """Main stream: after the guarded wgrad (before overwriting its operand in place) --
-        unless a segment ended since it was recorded (the segment end joined the branch)."""
-        if self.event is not None and self.event[1] == self._key():
-            self.main.wait_event(self.event[0])
-        self.event = None
-
-    def join(self, keep=False):
-        if not self._stale():
-            self.main.wait_stream(self.s)
-        if not keep:
-            self.keep, self.kept, self.event = [], 0, None
-
-
-_ACTIVE_BRANCH = None  # the weight-gradient branch of the backward in progress (grad_ready)
-
-
-def _wgrad(br, *args, guard=False, **kw):
-    if br is None:
-        wgrad_into(*args, **kw)
-    else:
-        br.run(*args, guard=guard, **kw)
-
-
 # CELU joins (BasicBlock, reference resnet.py:188-190): the backward takes act'(z) = exp(z/alpha)
 # from the fp32 pre-activation z = y*s + t + shortcut, recomputed from the stored bf16 branch
 # outputs exactly as the forward join formed it.  FDT_CELU_ZGRAD=0 restores the old derivative
@@ -755,17 +554,12 @@ class ResNetBodyFn(torch.autograd.Function):
             fs.pre_forward("conv1")
             plan.pack_stage("conv1", dev, fwd=True)
         recs = []
-        lay = plan.lazy_layout(x_nhwc.shape, dev)
         # stem: conv -> FCBN stats -> materialised CELU output
         st = plan.stem
-        y0, (s0, t0, sm0, sa0), M0, lz0 = conv_bn_fwd(x_nhwc, st, None, None, None, training, dev, lay=lay)
+        y0, (s0, t0, sm0, sa0), M0 = conv_bn_fwd(x_nhwc, st, None, None, None, training, dev)
         h = torch.empty_like(y0)
-        if lz0 is not None:
-            nat.act_affine_lazy(y0.data_ptr(), lz0[0], lz0[1], h.data_ptr(), M0, st.shp.cout, st.act_out[0],
-                                float(st.act_out[1]), 1, _sp())
-        else:
-            nat.act_affine_fwd(y0.data_ptr(), s0.data_ptr(), t0.data_ptr(), h.data_ptr(), M0, st.shp.cout,
-                               st.act_out[0], float(st.act_out[1]), 1, 1, _sp())
+        nat.act_affine_fwd(y0.data_ptr(), s0.data_ptr(), t0.data_ptr(), h.data_ptr(), M0, st.shp.cout,
+                           st.act_out[0], float(st.act_out[1]), 1, 1, _sp())
         stem_rec = (x_nhwc, y0, s0, t0, sm0, sa0)
         cur = "conv1"
         pending = None  # previous block's join, run inside this block's first conv
@@ -779,35 +573,29 @@ class ResNetBodyFn(torch.autograd.Function):
                 plan.pack_stage(cur, dev, fwd=True)
             x_in = h
             ys = []
-            raw, s, t, act, lz = x_in, None, None, (ACT_NONE, 1.0), None
+            raw, s, t, act = x_in, None, None, (ACT_NONE, 1.0)
             for ui, u in enumerate(b.units):
                 a_in = None
                 if ui == 0 and pending is not None:
                     # writes x_in (= the previous block's output) while staging it
-                    y, (su, tu, smu, sau), M, lzo = conv_bn_fwd_join(pending, u, training, dev, lay, pend_tile)
+                    y, (su, tu, smu, sau), M = conv_bn_fwd_join(pending, u, training, dev, pend_tile)
                     pending = None
                 elif MATERIALIZE_3X3 and u.shp.k > 1 and s is not None:
                     # 3x3: normalise + activate the input ONCE instead of in every one of the
-                    # 9 im2col re-reads of the conv's operand staging (lazy statistics: the
-                    # producer's finalize runs inside this pass)
+                    # 9 im2col re-reads of the conv's operand staging
                     a_in = torch.empty_like(raw)
-                    if lz is not None:
-                        nat.act_affine_lazy(raw.data_ptr(), lz[0], lz[1], a_in.data_ptr(), _rows(raw), raw.shape[-1],
-                                            act[0], float(act[1]), 1, _sp())
-                    else:
-                        nat.act_affine_fwd(raw.data_ptr(), s.data_ptr(), t.data_ptr(), a_in.data_ptr(), _rows(raw),
-                                           raw.shape[-1], act[0], float(act[1]), 1, 1, _sp())
-                    y, (su, tu, smu, sau), M, lzo = conv_bn_fwd(a_in, u, None, None, None, training, dev, lay=lay)
+                    nat.act_affine_fwd(raw.data_ptr(), s.data_ptr(), t.data_ptr(), a_in.data_ptr(), _rows(raw),
+                                       raw.shape[-1], act[0], float(act[1]), 1, 1, _sp())
+                    y, (su, tu, smu, sau), M = conv_bn_fwd(a_in, u, None, None, None, training, dev)
                 else:
-                    y, (su, tu, smu, sau), M, lzo = conv_bn_fwd(raw, u, s, t, act, training, dev, lazy_in=lz,
-                                                                lay=lay)
+                    y, (su, tu, smu, sau), M = conv_bn_fwd(raw, u, s, t, act, training, dev)
                 ys.append((y, su, tu, smu, sau, M, a_in))
-                raw, s, t, act, lz = y, su, tu, u.act_out, lzo
-            y3, s3, t3, lz3 = ys[-1][0], ys[-1][1], ys[-1][2], lz
-            sc, lzsc = None, None
+                raw, s, t, act = y, su, tu, u.act_out
+            y3, s3, t3 = ys[-1][0], ys[-1][1], ys[-1][2]
+            sc = None
             if b.shortcut is not None:
                 u = b.shortcut
-                ysc, (ssc, tsc, smsc, sasc), M, lzsc = conv_bn_fwd(x_in, u, None, None, None, training, dev, lay=lay)
+                ysc, (ssc, tsc, smsc, sasc), M = conv_bn_fwd(x_in, u, None, None, None, training, dev)
                 sc = (ysc, ssc, tsc, smsc, sasc, M, None)
             out = torch.empty_like(y3)
             C = y3.shape[-1]
@@ -821,14 +609,7 @@ class ResNetBodyFn(torch.autograd.Function):
             if pend_tile is not None:
                 # the next block's first 1x1 conv computes this join while staging its operand
                 # and stores `out` + mask (one pass instead of join pass + operand re-read)
-                pending = (y3, s3, t3, sc[0] if sc else x_in, sc[1] if sc else None, sc[2] if sc else None, out, mask,
-                           lz3, lzsc)
-            elif lz3 is not None:
-                lzb = lzsc if lzsc is not None else ([], [])
-                nat.residual_act_lazy(y3.data_ptr(), lz3[0], lz3[1], _p(sc[0] if sc else None), lzb[0], lzb[1],
-                                      _p(sc[1] if sc and lzsc is None else None),
-                                      _p(sc[2] if sc and lzsc is None else None), 0 if sc else x_in.data_ptr(),
-                                      out.data_ptr(), _p(mask), _rows(y3), C, b.join[0], float(b.join[1]), 1, _sp())
+                pending = (y3, s3, t3, sc[0] if sc else x_in, sc[1] if sc else None, sc[2] if sc else None, out, mask)
             else:
                 nat.residual_act_fwd(y3.data_ptr(), s3.data_ptr(), t3.data_ptr(), _p(sc[0] if sc else None),
                                      _p(sc[1] if sc else None), _p(sc[2] if sc else None),
@@ -870,16 +651,6 @@ class ResNetBodyFn(torch.autograd.Function):
         recs = ctx.recs
         nblk = len(plan.blocks)
         fs = plan.fsdp
-        global _ACTIVE_BRANCH
-        br = _ACTIVE_BRANCH = _WgradBranch.make(dev)
-        try:
-            return ResNetBodyFn._backward_blocks(ctx, plan, training, g, ghw, dev, recs, nblk, fs, br)
-        finally:
-            _ACTIVE_BRANCH = None
-
-    @staticmethod
-    def _backward_blocks(ctx, plan, training, g, ghw, dev, recs, nblk, fs, br):
-        nat = _native.native()
         joined = False  # g is already g_pre of the current block (its BN-backward coefficients
         joined_coef = None  # computed with the dgrad that completed it: joined_coef)
         cur = None
@@ -887,8 +658,6 @@ class ResNetBodyFn(torch.autograd.Function):
             b = plan.blocks[bi]
             if fs is not None and plan.stage_of[bi] != cur:
                 if cur is not None:
-                    if br is not None:
-                        br.join()  # the stage's gradients are complete before its reduce-scatter
                     plan.release_stage(cur, fwd=False)
                     fs.post_backward(cur)
                 cur = plan.stage_of[bi]
@@ -923,7 +692,7 @@ class ResNetBodyFn(torch.autograd.Function):
                 als, bes = coef_sc
                 g_x, _ = ci.conv_dgrad(gpre, sc[0], als, bes, u.wd, u.shp, tuple(x_in.shape), epi=ci.EPI_STORE,
                                        gs=sc[1])
-                _wgrad(br, u, gpre, sc[0], als, bes, x_in, None, None, (ACT_NONE, 1.0), gs=sc[1])
+                wgrad_into(u, gpre, sc[0], als, bes, x_in, None, None, (ACT_NONE, 1.0), gs=sc[1])
             else:
                 g_x = gpre  # identity: the x_in gradient accumulates onto g_pre in place
             # the block whose output is x_in: its join backward runs in the epilogue of the
@@ -939,7 +708,7 @@ class ResNetBodyFn(torch.autograd.Function):
                 if i > 0:
                     yp, sp_, tp = ys[i - 1][0], ys[i - 1][1], ys[i - 1][2]
                     actp = b.units[i - 1].act_out
-                    pp = slots(2, u.shp.cin, dev, _rows(yp), u.shp.k > 1)
+                    pp = slots(2, u.shp.cin, dev, _rows(yp))
                     up = b.units[i - 1]
                     cf, (al_p, be_p), _ = coef_args(up, (ys[i - 1][3], ys[i - 1][4], ys[i - 1][5]),
                                                     training=training, dev=dev)
@@ -952,23 +721,18 @@ class ResNetBodyFn(torch.autograd.Function):
                         g_prev, _ = ci.conv_dgrad(gf, None, None, None, u.wd, u.shp, tuple(yp.shape),
                                                   epi=ci.EPI_ACTBWD, ex=yp, es=sp_, et=tp, act=actp[0],
                                                   alpha=actp[1], part=pp, coef=cf)
-                        _wgrad(br, u, gf, None, None, None, a_in if a_in is not None else yp,
-                               None if a_in is not None else sp_, None if a_in is not None else tp,
-                               (ACT_NONE, 1.0) if a_in is not None else actp)
+                        wgrad_into(u, gf, None, None, None, a_in if a_in is not None else yp,
+                                   None if a_in is not None else sp_, None if a_in is not None else tp,
+                                   (ACT_NONE, 1.0) if a_in is not None else actp)
                     else:
                         g_prev, _ = ci.conv_dgrad(g_cur, y, al, be, u.wd, u.shp, tuple(yp.shape),
                                                   epi=ci.EPI_ACTBWD, ex=yp, es=sp_, et=tp, act=actp[0],
                                                   alpha=actp[1], part=pp, gs=gs_cur, coef=cf)
-                        # (the last unit reads g_pre: an identity block's first-unit dgrad
-                        # later accumulates into it in place -- guarded)
-                        _wgrad(br, u, g_cur, y, al, be, yp, sp_, tp, actp, gs=gs_cur,
-                               guard=(i == len(b.units) - 1 and sc is None))
+                        wgrad_into(u, g_cur, y, al, be, yp, sp_, tp, actp, gs=gs_cur)
                     coef_ready(up)
                     al, be = al_p, be_p
                     g_cur, gs_cur = g_prev, None
                 else:
-                    if br is not None and sc is None:
-                        br.wait()  # g_x aliases g_pre: its last reader (a branch wgrad) first
                     if prev is not None:
                         px_in, pys, psc, pout, pmask = prec
                         pjz = _celu_jz(prev, pys, psc, px_in)
@@ -987,12 +751,10 @@ class ResNetBodyFn(torch.autograd.Function):
                     else:
                         ci.conv_dgrad(g_cur, y, al, be, u.wd, u.shp, tuple(x_in.shape), epi=ci.EPI_ADD, out=g_x,
                                       gs=gs_cur)
-                    _wgrad(br, u, g_cur, y, al, be, x_in, None, None, (ACT_NONE, 1.0), gs=gs_cur)
+                    wgrad_into(u, g_cur, y, al, be, x_in, None, None, (ACT_NONE, 1.0), gs=gs_cur)
             g = g_x
             joined = prev is not None
         if fs is not None and cur is not None:
-            if br is not None:
-                br.join()
             plan.release_stage(cur, fwd=False)
             fs.post_backward(cur)
             fs.pre_backward("conv1")
@@ -1006,9 +768,7 @@ class ResNetBodyFn(torch.autograd.Function):
         nat.act_bwd_reduce(g.data_ptr(), y0.data_ptr(), s0.data_ptr(), t0.data_ptr(), gy0.data_ptr(),
                            part.data_ptr(), part.shape[0], M0, C0, st.act_out[0], float(st.act_out[1]), 1, _sp())
         (al, be), _ = bwd_finalize(part, 2, st, (sm0, sa0, M0), training=training, dev=dev)
-        _wgrad(br, st, gy0, y0, al, be, x_img, None, None, (ACT_NONE, 1.0))
-        if br is not None:
-            br.join()
+        wgrad_into(st, gy0, y0, al, be, x_img, None, None, (ACT_NONE, 1.0))
         if fs is not None:
             fs.post_backward("conv1")
         if not getattr(ctx, "keep", False):
