@@ -1,4 +1,4 @@
-"""CIFAR-10 data: dataset files, device-resident batches, GPU augmentation.
+"""CIFAR-10 / CIFAR-100 data: dataset files, device-resident batches, GPU augmentation.
 
 Reference: ``CIFAR10`` / ``VisionDataset`` (``resnet50_test.py:62-292``: pickled batches
 kept as uint8 NHWC in RAM, per-sample float conversion), the scripted augmentation
@@ -46,9 +46,34 @@ URL = "https://www.cs.toronto.edu/~kriz/cifar-10-python.tar.gz"
 FILENAME = "cifar-10-python.tar.gz"
 TGZ_MD5 = "c58f30108f718f92721af3b95e74349a"
 
+# CIFAR-100 (python format: one "train", one "test" and a "meta" file).  The URL and the MD5s are
+# torchvision's constants written down from memory: neither torchvision nor the archive was at
+# hand to re-verify them, so a mismatch on the first real download means a constant here is wrong.
+C100_TRAIN_LIST = [("train", "16019d7e3df5930d79c1b9d7a5e64d7c")]
+C100_TEST_LIST = [("test", "f0ef6b0ae62326f3e7ffdfab6717acfc")]
+C100_META = ("meta", "7973b15100ade9c7d40fb424638fde48")
+C100_BASE_FOLDER = "cifar-100-python"
+C100_BIN_FOLDER = "cifar-100-binary"
+C100_URL = "https://www.cs.toronto.edu/~kriz/cifar-100-python.tar.gz"
+C100_FILENAME = "cifar-100-python.tar.gz"
+C100_TGZ_MD5 = "eb9058c3a382ffc7106e4002c42a8d85"
 
-def get_classes():
-    return CLASSES
+
+def get_classes(dataset="cifar10", root="./data"):
+    """Class names: the fixed CIFAR-10 tuple, or for ``"cifar100"`` the 100 ``fine_label_names`` of
+    the data set's ``meta`` file under ``root`` (binary distribution: ``fine_label_names.txt``)."""
+    if dataset == "cifar10":
+        return CLASSES
+    if dataset != "cifar100":
+        raise ValueError(f"unknown data set {dataset!r}")
+    meta = os.path.join(root, C100_BASE_FOLDER, C100_META[0])
+    if os.path.isfile(meta):
+        return tuple(_unpickle(meta)["fine_label_names"])
+    txt = os.path.join(root, C100_BIN_FOLDER, "fine_label_names.txt")
+    if os.path.isfile(txt):
+        with open(txt) as f:
+            return tuple(line.strip() for line in f if line.strip())
+    raise RuntimeError(f"CIFAR-100 class names not found under {root}")
 
 
 class _NumpyOnlyUnpickler(pickle.Unpickler):
@@ -64,18 +89,24 @@ class _NumpyOnlyUnpickler(pickle.Unpickler):
         raise pickle.UnpicklingError(f"refusing to load {module}.{name} from a CIFAR batch file")
 
 
-def _load_batch(path):
+def _unpickle(path):
     with open(path, "rb") as f:
-        entry = _NumpyOnlyUnpickler(io.BytesIO(f.read()), encoding="latin1").load()
+        return _NumpyOnlyUnpickler(io.BytesIO(f.read()), encoding="latin1").load()
+
+
+def _load_batch(path):
+    entry = _unpickle(path)
     data = np.asarray(entry["data"], dtype=np.uint8).reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1)
     labels = entry["labels"] if "labels" in entry else entry["fine_labels"]
     return np.ascontiguousarray(data), np.asarray(labels, dtype=np.int64)
 
 
-def _load_bin(path):
-    raw = np.fromfile(path, dtype=np.uint8).reshape(-1, 3073)
-    labels = raw[:, 0].astype(np.int64)
-    data = raw[:, 1:].reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1)
+def _load_bin(path, label_bytes=1):
+    """Binary rows: ``label_bytes`` label bytes (CIFAR-100: coarse, fine -- the last one is the
+    label) followed by 3072 pixel bytes."""
+    raw = np.fromfile(path, dtype=np.uint8).reshape(-1, label_bytes + 3072)
+    labels = raw[:, label_bytes - 1].astype(np.int64)
+    data = raw[:, label_bytes:].reshape(-1, 3, 32, 32).transpose(0, 2, 3, 1)
     return np.ascontiguousarray(data), labels
 
 
@@ -84,6 +115,15 @@ class CIFAR10:
     batches (``cifar-10-batches-py``, numpy-only unpickler) or the binary batches
     (``cifar-10-batches-bin``).  ``__getitem__`` returns (float CHW tensor, label) with
     the optional transform, for API parity with the reference class."""
+    name = "CIFAR-10"
+    num_classes = 10
+    label_bytes = 1  # of a binary row
+
+    def _files(self):
+        """The file lists and archive constants, read from the module when used."""
+        return dict(folder=BASE_FOLDER, bin_folder="cifar-10-batches-bin", train=TRAIN_LIST, test=TEST_LIST, extra=[],
+                    bin_train=[f"data_batch_{i}.bin" for i in range(1, 6)], bin_test=["test_batch.bin"],
+                    url=URL, filename=FILENAME, md5=TGZ_MD5)
 
     def __init__(self, root="./data", train=True, transform=None, target_transform=None, download=False):
         self.root = root
@@ -95,28 +135,31 @@ class CIFAR10:
         self.data, self.targets = self._load()
 
     def _load(self):
-        pyd = os.path.join(self.root, BASE_FOLDER)
-        bind = os.path.join(self.root, "cifar-10-batches-bin")
+        fs = self._files()
+        pyd = os.path.join(self.root, fs["folder"])
+        bind = os.path.join(self.root, fs["bin_folder"])
         if os.path.isdir(pyd):
-            names = [n for n, _ in (TRAIN_LIST if self.train else TEST_LIST)]
+            names = [n for n, _ in (fs["train"] if self.train else fs["test"])]
             parts = [_load_batch(os.path.join(pyd, n)) for n in names]
         elif os.path.isdir(bind):
-            names = [f"data_batch_{i}.bin" for i in range(1, 6)] if self.train else ["test_batch.bin"]
-            parts = [_load_bin(os.path.join(bind, n)) for n in names]
+            names = fs["bin_train"] if self.train else fs["bin_test"]
+            parts = [_load_bin(os.path.join(bind, n), self.label_bytes) for n in names]
         else:
-            raise RuntimeError(f"CIFAR-10 not found under {self.root} (use download=True or synthetic data)")
+            raise RuntimeError(f"{self.name} not found under {self.root} (use download=True or synthetic data)")
         return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
 
     def _check_integrity(self):
         from .download import check_integrity
-        pyd = os.path.join(self.root, BASE_FOLDER)
-        return all(check_integrity(os.path.join(pyd, n), md5) for n, md5 in TRAIN_LIST + TEST_LIST)
+        fs = self._files()
+        pyd = os.path.join(self.root, fs["folder"])
+        return all(check_integrity(os.path.join(pyd, n), md5) for n, md5 in fs["train"] + fs["test"] + fs["extra"])
 
     def download(self):
         from .download import download_and_extract_archive
-        if os.path.isdir(os.path.join(self.root, BASE_FOLDER)) and self._check_integrity():
+        fs = self._files()
+        if os.path.isdir(os.path.join(self.root, fs["folder"])) and self._check_integrity():
             return
-        download_and_extract_archive(URL, self.root, filename=FILENAME, md5=TGZ_MD5)
+        download_and_extract_archive(fs["url"], self.root, filename=fs["filename"], md5=fs["md5"])
 
     def __len__(self):
         return len(self.data)
@@ -129,6 +172,26 @@ class CIFAR10:
         if self.target_transform is not None:
             t = self.target_transform(t)
         return img, t
+
+
+class CIFAR100(CIFAR10):
+    """CIFAR-100 with its 100 fine labels (the 20 coarse ones are not used): the python format
+    (``cifar-100-python``: ``train`` / ``test`` / ``meta``, labels from ``fine_labels``) or the binary
+    one (``cifar-100-binary``: ``train.bin`` / ``test.bin``, rows of coarse label, fine label, 3072
+    pixels).  Same constructor and ``__getitem__`` as ``CIFAR10``.  The loaders normalise both sets
+    with ``CIFAR_MEAN`` / ``CIFAR_STD``, the CIFAR-10 constants -- the reference's habit, and the
+    augmentation kernel and its tests stay as they are."""
+    name = "CIFAR-100"
+    num_classes = 100
+    label_bytes = 2
+
+    def _files(self):
+        return dict(folder=C100_BASE_FOLDER, bin_folder=C100_BIN_FOLDER, train=C100_TRAIN_LIST, test=C100_TEST_LIST,
+                    extra=[C100_META], bin_train=["train.bin"], bin_test=["test.bin"],
+                    url=C100_URL, filename=C100_FILENAME, md5=C100_TGZ_MD5)
+
+
+DATASETS = {"cifar10": CIFAR10, "cifar100": CIFAR100}
 
 
 def synthetic_cifar(n=50000, num_classes=10, seed=0, hw=32):

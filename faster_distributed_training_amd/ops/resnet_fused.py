@@ -54,6 +54,7 @@ JOIN_FOLD_MIN_M = int(os.environ.get("FDT_JOIN_FOLD_MIN_M", str(1 << 18)))
 # run the classifier head (average pool + fc, bf16 autocast numerics) as two engine kernels
 # inside the body's graphs instead of eager PyTorch ops (see csrc/kernels/head.hip)
 FUSED_HEAD = os.environ.get("FDT_FUSED_HEAD", "1") != "0"
+HEAD_MAX_CLASSES = 256  # head.hip's cap (CIFAR-100, Tiny-ImageNet's 200); wider heads run as PyTorch ops
 MODE_FCBN, MODE_BN_TRAIN, MODE_BN_EVAL, MODE_FCBN_TRACK = 0, 1, 2, 3
 BF16 = torch.bfloat16
 
@@ -779,7 +780,9 @@ class ResNetBodyFn(torch.autograd.Function):
 # ------------------------------------------------------------------ classifier head
 def head_fusable(model, x, need_grad) -> bool:
     """The fused head reproduces ``fc(mean_hw(body))`` under bf16 autocast for heads of at
-    most 32 classes with fp32 parameters / gradients; anything else keeps the PyTorch ops."""
+    most 256 classes with fp32 parameters / gradients (csrc/kernels/head.hip: up to 32 classes
+    any width that is a multiple of 8; above, the MFMA head, whose tiles need a multiple of 32
+    channels); anything else keeps the PyTorch ops."""
     fc = getattr(model, "fc", None)
     if not FUSED_HEAD or not getattr(model, "fused_head", True) or not isinstance(fc, nn.Linear) or fc.bias is None or getattr(model, "_fsdp", None) is not None:
         return False
@@ -791,7 +794,7 @@ def head_fusable(model, x, need_grad) -> bool:
     if not hasattr(_native.native(), "head_fwd"):
         return False
     K, C = fc.weight.shape
-    if K > 32 or C % 8:
+    if K > HEAD_MAX_CLASSES or C % (32 if K > 32 else 8):
         return False
     for p in (fc.weight, fc.bias):
         if p.dtype != torch.float32 or not p.is_contiguous() or (need_grad and not p.requires_grad):

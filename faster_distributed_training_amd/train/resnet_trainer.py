@@ -1,4 +1,4 @@
-"""ResNet / CIFAR-10 training driver (reference ``resnet50_test.py:460-740``; T1, T2, T5).
+"""ResNet / CIFAR-10 and CIFAR-100 training driver (reference ``resnet50_test.py:460-740``; T1, T2, T5).
 
 Per step (all on device, no host synchronisation):
   batch (device-resident CIFAR + GPU augment) -> mixup (A1) or meta-mixup (A2) ->
@@ -19,7 +19,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from ..data.cifar import CLASSES, CIFAR10, DeviceCIFARLoader, augment_order, synthetic_cifar
+from ..data.cifar import DATASETS, DeviceCIFARLoader, augment_order, synthetic_cifar
 from ..models import resnet as resnet_models
 from ..ops.mixup import unit_grad, MetaMixup, mixup_criterion, mixup_criterion_meta, mixup_data
 from ..ops.resnet_fused import STAGES
@@ -36,7 +36,8 @@ from .metrics import DeviceMeter, JsonlLogger, PhaseProfiler, draw_graph, peak_m
 @dataclass
 class ResNetConfig:
     arch: str = "resnet50"
-    num_classes: int = 10
+    dataset: str = "cifar10"           # cifar10 | cifar100 (100 fine labels; its own checkpoint files, top-5 in test)
+    num_classes: int | None = None     # None: the data set's (10 / 100); cifar100 accepts no other value
     bs: int = 128                      # per process (reference --bs)
     lr: float = 0.02
     epoch: int = 50
@@ -88,6 +89,15 @@ class ResNetConfig:
                                        # on this many un-mixed, augmented training batches
     eval_only: bool = False            # with resume: load, (calibrate,) evaluate once; no training
     extra: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        if self.dataset not in DATASETS:
+            raise ValueError(f"dataset must be one of {sorted(DATASETS)}, not {self.dataset!r}")
+        n = DATASETS[self.dataset].num_classes
+        if self.num_classes is None:
+            self.num_classes = n
+        elif self.dataset == "cifar100" and self.num_classes != n:
+            raise ValueError(f"dataset 'cifar100' has {n} classes: num_classes={self.num_classes} conflicts")
 
 
 def check_eval_config(eval_stats: str, fsdp: bool = False, calibrate_batches: int = 0, eval_only: bool = False,
@@ -210,7 +220,9 @@ class ResNetTrainer:
     # ------------------------------------------------------------------ setup
     @property
     def ckpt_path(self):
-        return os.path.join(self.cfg.checkpoint_dir, "resnet_ckpt.pth")
+        # (a 100-class run neither resumes from nor overwrites the 10-class files; *_last follows)
+        name = "resnet_ckpt.pth" if self.cfg.dataset == "cifar10" else f"resnet_{self.cfg.dataset}_ckpt.pth"
+        return os.path.join(self.cfg.checkpoint_dir, name)
 
     @property
     def last_path(self):
@@ -304,10 +316,11 @@ class ResNetTrainer:
             tr = synthetic_cifar(50000, cfg.num_classes, seed=1)
             te = synthetic_cifar(10000, cfg.num_classes, seed=2)
         else:
+            ds = DATASETS[cfg.dataset]
             if self.rank == 0:
-                CIFAR10(cfg.data_root, train=True, download=True)
+                ds(cfg.data_root, train=True, download=True)
             pdist.barrier()
-            a, b = CIFAR10(cfg.data_root, train=True), CIFAR10(cfg.data_root, train=False)
+            a, b = ds(cfg.data_root, train=True), ds(cfg.data_root, train=False)
             tr, te = (a.data, a.targets), (b.data, b.targets)
         sub = cfg.extra.get("subset_stride")  # tuning: strided 10% subset (C7)
         if sub:
@@ -435,16 +448,24 @@ class ResNetTrainer:
         total = torch.zeros((), device=self.device)
         loss_sum = torch.zeros((), device=self.device)
         crit = nn.CrossEntropyLoss(reduction="sum")
+        top5 = self.cfg.dataset == "cifar100"  # (accumulated on the device like the rest: no sync per batch)
+        correct5 = torch.zeros((), device=self.device)
         for x, y in self.test_loader:
             with self._autocast():
                 out = self.model(x)
             loss_sum += crit(out.float(), y)
             correct += (out.argmax(1) == y).sum()
+            if top5:
+                correct5 += (out.topk(5, dim=1).indices == y.view(-1, 1)).any(1).sum()
             total += y.numel()
         acc = 100.0 * float(correct) / max(float(total), 1.0)
         acc = pdist.broadcast_scalar(acc)  # one decision for all ranks (save_checkpoint is collective)
         self.testing_acc.append(acc)
-        print0(f"test epoch {epoch}: acc {acc:.2f}% loss {float(loss_sum) / max(float(total), 1):.4f}")
+        if top5:
+            acc5 = pdist.broadcast_scalar(100.0 * float(correct5) / max(float(total), 1.0))
+            print0(f"test epoch {epoch}: acc {acc:.2f}% top-5 {acc5:.2f}% loss {float(loss_sum) / max(float(total), 1):.4f}")
+        else:
+            print0(f"test epoch {epoch}: acc {acc:.2f}% loss {float(loss_sum) / max(float(total), 1):.4f}")
         if save and acc > self.best_acc:
             prefix = self.cfg.distributed or (not self.cfg.distributed and self.cfg.faithful)
             extra = {"optimizer": self.optimizer.state_dict()} if self.cfg.extra.get("save_optimizer") else None
@@ -453,7 +474,10 @@ class ResNetTrainer:
                 extra = dict(extra or {}, fused_stats=stats)
             ckpt.save_checkpoint(self.ckpt_path, self.model, acc, epoch, module_prefix=prefix, extra=extra)
             self.best_acc = acc
-        self.logger.log(epoch=epoch, test_acc=acc)
+        if top5:
+            self.logger.log(epoch=epoch, test_acc=acc, test_top5=acc5)
+        else:
+            self.logger.log(epoch=epoch, test_acc=acc)
         return acc
 
     def evaluate_only(self):

@@ -9,12 +9,17 @@ the inference switches:
                                  before each evaluation
   --eval_only                    with --resume: load, (calibrate,) evaluate once and exit
 
+and the data set switch:
+
+  --dataset {cifar10,cifar100}   cifar100: 100 fine labels, checkpoints resnet_cifar100_*.pth, top-5 in the evaluation
+
 Without the new switches it behaves exactly like ``resnet50_test.py``.
 
 Examples:
     python resnet_infer.py --eval_stats running                       # track statistics, evaluate frozen
     python resnet_infer.py --eval_stats running --resume --eval_only --bs 1
     python resnet_infer.py --eval_stats running --calibrate_batches 8 --resume --eval_only
+    python resnet_infer.py --dataset cifar100 --synthetic --bs 256 --epoch 1
 """
 from __future__ import annotations
 
@@ -38,6 +43,9 @@ def parse(argv=None):
     p.add_argument("--calibrate_batches", default=0, type=int,
                    help="before each evaluation, re-estimate the running statistics on N clean training batches")
     p.add_argument("--eval_only", action="store_true", help="with --resume: load, (calibrate,) evaluate once and exit")
+    p.add_argument("--dataset", default="cifar10", choices=["cifar10", "cifar100"],
+                   help="cifar100: the 100 fine labels, a 100-class head, checkpoints in resnet_cifar100_*.pth, "
+                        "top-5 accuracy in the evaluation")
     argv = list(sys.argv[1:] if argv is None else argv)
     if "-h" in argv or "--help" in argv:
         p.print_help()
@@ -53,8 +61,10 @@ def parse(argv=None):
 
 
 def config_from_args(a, base):
+    # (num_classes=None: the data set decides)
     return dataclasses.replace(resnet50_test.config_from_args(base), eval_stats=a.eval_stats,
-                               calibrate_batches=a.calibrate_batches, eval_only=a.eval_only)
+                               calibrate_batches=a.calibrate_batches, eval_only=a.eval_only,
+                               dataset=a.dataset, num_classes=None)
 
 
 def main(argv=None):
