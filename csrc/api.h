@@ -138,10 +138,10 @@ void pack_weights(const std::vector<uint64_t>& src, const std::vector<uint64_t>&
 // eigh.hip
 void jacobi_eigh(uint64_t A, uint64_t w, uint64_t V, uint64_t table, int batch, int n, int max_sweeps, float tol, uint64_t stream);
 // attention.hip
-void attn_fwd(uint64_t q, uint64_t k, uint64_t v, const std::vector<long>& strides, uint64_t out, uint64_t lse,
-              uint64_t mask, int B, int L, int H, float fill, float p_drop, uint64_t seed, uint64_t seed_ptr,
-              uint64_t stream);
-void attn_bwd(uint64_t q, uint64_t k, uint64_t v, const std::vector<long>& strides, uint64_t o, uint64_t dout,
+void attn_fwd(uint64_t q, uint64_t k, uint64_t v, const std::vector<long>& strides, uint64_t out, uint64_t out32,
+              uint64_t lse, uint64_t mask, int B, int L, int H, float fill, float p_drop, uint64_t seed,
+              uint64_t seed_ptr, uint64_t stream);
+void attn_bwd(uint64_t q, uint64_t k, uint64_t v, const std::vector<long>& strides, uint64_t o32, uint64_t dout,
               uint64_t lse, uint64_t delta, uint64_t mask, uint64_t dq, uint64_t dk, uint64_t dv, int B, int L, int H,
               float fill, float p_drop, uint64_t seed, uint64_t seed_ptr, long grad_ld, uint64_t stream);
 // dropout.hip

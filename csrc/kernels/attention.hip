@@ -9,6 +9,10 @@
 // copies); O / dO / dQ / dK / dV are contiguous (B, L, H, 64); the log-sum-exp and
 // delta = rowsum(dO * O) are (B, H, L) fp32.  Scores live in the log2 domain
 // (x = s * log2(e)/sqrt(d)); exp2 everywhere.
+// delta is taken from an fp32 copy of O that the forward writes next to the bf16 output when
+// a backward will follow: dS = P (dP - delta) cancels almost completely in a row whose softmax
+// is nearly one-hot, and the bf16 rounding of O put an absolute error of ~2^-9 |dO||O| into
+// delta, i.e. into dQ and dK, which in such rows is larger than the gradient itself.
 //
 // MFMA mapping (mfma_f32_32x32x16_bf16; C[row][col]: col = lane & 31, row = (r&3) + 8(r>>2)
 // + 4(lane>>5)): every product is oriented so that the accumulator of the first GEMM is
@@ -17,12 +21,14 @@
 // same permuted order from the row image itself with the gfx950 transposing LDS read
 // (ds_read_b64_tr_b16, two per fragment) -- no transposed copy is staged.
 //   forward     S^T = K Q^T (query on the lane -> row max / sum are in-register plus one
-//               lane^32 exchange), online softmax, O^T += V^T P^T.          grid (L/128, H, B)
+//               lane^32 exchange), online softmax, O^T += V^T P^T.    grid (ceil(L/128), H, B)
 //   bwd dK,dV   S = Q K^T, dP = dO V^T (key on the lane), dV^T += dO^T P, dK^T += Q^T dS:
-//               each wave owns 32 keys, the workgroup sweeps all queries.   grid (L/128, H, B)
+//               each wave owns 32 keys, the workgroup sweeps all queries.   same grid
 //   bwd dQ      S^T, dP^T as in forward, dQ^T += K^T dS^T: each wave owns 32 queries,
 //               the workgroup sweeps all keys (recomputes P instead of atomics / a dS
-//               round trip -- at L <= 512 the kernels are latency-, not FLOP-bound).
+//               round trip -- at L <= 512 the kernels are latency-, not FLOP-bound).   same grid
+// The last workgroup of a row is partial when L is no multiple of 128: its absent rows are
+// clamped to L - 1 for the loads and never stored.
 // Masking: keys past L are absent; key-padding-masked keys get the fill value (-inf = true
 // mask; the reference's -1e-9 fill, survey Q7, is reproduced with fill = -1e-9).  Dropout:
 // a counter-based hash of (seed, b, h, q, key) -- the same keep mask in all kernels, no
@@ -46,9 +52,10 @@ struct Args {
   const bf16* k;
   const bf16* v;
   long qb, ql, qh, kb, kl, kh, vb, vl, vh;  // element strides (batch, position, head); d contiguous
-  const bf16* o;                            // forward output [B][L][H][D]
+  const float* o32;                         // forward output before rounding [B][L][H][D]
   const bf16* dout;                         // [B][L][H][D]
   bf16* out;
+  float* out32;  // optional unrounded copy of out for the backward's delta; nullptr = not kept
   bf16* dq;
   bf16* dk;
   bf16* dv;
@@ -242,25 +249,35 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void a
                                    pack_bf16x2(oacc[dt][4 * g + 2] * inv, oacc[dt][4 * g + 3] * inv));
         *reinterpret_cast<uint2*>(op + 32 * dt + 8 * g + 4 * h) = u;
       }
+    if (a.out32 != nullptr) {
+      float* op32 = a.out32 + (((long)b * a.L + q) * a.H + hd) * kD;
+#pragma unroll
+      for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          *reinterpret_cast<float4*>(op32 + 32 * dt + 8 * g + 4 * h) =
+              make_float4(oacc[dt][4 * g] * inv, oacc[dt][4 * g + 1] * inv, oacc[dt][4 * g + 2] * inv,
+                          oacc[dt][4 * g + 3] * inv);
+    }
     if (h == 0) a.lse[(long)bh * a.L + q] = l > 0.f ? m + log2f(l) : -INFINITY;
   }
 }
 
 // ------------------------------------------------------------------------------ backward
-// delta[b][h][q] = sum_d dO * O   (one thread per (b, q, h) row of 64)
+// delta[b][h][q] = sum_d dO * O, O unrounded   (one thread per (b, q, h) row of 64)
 __global__ __launch_bounds__(256) void attn_bwd_prep_kernel(Args a) {
   const long row = (long)blockIdx.x * 256 + threadIdx.x;
   if (row >= (long)a.B * a.L * a.H) return;
-  const bf16* o = a.o + row * kD;
+  const float* o = a.o32 + row * kD;
   const bf16* g = a.dout + row * kD;
   float acc = 0.f;
 #pragma unroll
   for (int c = 0; c < 8; ++c) {
-    const uint4 uo = *reinterpret_cast<const uint4*>(o + 8 * c);
+    const float4 o0 = *reinterpret_cast<const float4*>(o + 8 * c);
+    const float4 o1 = *reinterpret_cast<const float4*>(o + 8 * c + 4);
     const uint4 ug = *reinterpret_cast<const uint4*>(g + 8 * c);
-    const uint32_t po[4] = {uo.x, uo.y, uo.z, uo.w}, pg[4] = {ug.x, ug.y, ug.z, ug.w};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) acc += bf16_lo(po[e]) * bf16_lo(pg[e]) + bf16_hi(po[e]) * bf16_hi(pg[e]);
+    acc += o0.x * bf16_lo(ug.x) + o0.y * bf16_hi(ug.x) + o0.z * bf16_lo(ug.y) + o0.w * bf16_hi(ug.y);
+    acc += o1.x * bf16_lo(ug.z) + o1.y * bf16_hi(ug.z) + o1.z * bf16_lo(ug.w) + o1.w * bf16_hi(ug.w);
   }
   const int hd = (int)(row % a.H);
   const long bl = row / a.H;
@@ -480,12 +497,13 @@ static Args make_args(uint64_t q, uint64_t k, uint64_t v, const std::vector<long
 
 }  // namespace attn
 
-void attn_fwd(uint64_t q, uint64_t k, uint64_t v, const std::vector<long>& strides, uint64_t out, uint64_t lse,
-              uint64_t mask, int B, int L, int H, float fill, float p_drop, uint64_t seed, uint64_t seed_ptr,
-              uint64_t stream) {
+void attn_fwd(uint64_t q, uint64_t k, uint64_t v, const std::vector<long>& strides, uint64_t out, uint64_t out32,
+              uint64_t lse, uint64_t mask, int B, int L, int H, float fill, float p_drop, uint64_t seed,
+              uint64_t seed_ptr, uint64_t stream) {
   using namespace attn;
   Args a = make_args(q, k, v, strides, mask, B, L, H, fill, p_drop, seed, seed_ptr);
   a.out = P<bf16>(out);
+  a.out32 = P<float>(out32);
   a.lse = P<float>(lse);
   const dim3 grid((L + kBlk - 1) / kBlk, H, B);
   if (a.drop_thr) hipLaunchKernelGGL(attn_fwd_kernel<true>, grid, dim3(256), 0, as_stream(stream), a);
@@ -493,14 +511,15 @@ void attn_fwd(uint64_t q, uint64_t k, uint64_t v, const std::vector<long>& strid
   FDT_LAUNCH_CHECK();
 }
 
-void attn_bwd(uint64_t q, uint64_t k, uint64_t v, const std::vector<long>& strides, uint64_t o, uint64_t dout,
+void attn_bwd(uint64_t q, uint64_t k, uint64_t v, const std::vector<long>& strides, uint64_t o32, uint64_t dout,
               uint64_t lse, uint64_t delta, uint64_t mask, uint64_t dq, uint64_t dk, uint64_t dv, int B, int L, int H,
               float fill, float p_drop, uint64_t seed, uint64_t seed_ptr, long grad_ld, uint64_t stream) {
   using namespace attn;
   Args a = make_args(q, k, v, strides, mask, B, L, H, fill, p_drop, seed, seed_ptr);
   FDT_CHECK(grad_ld == 0 || (grad_ld >= (long)H * kD && grad_ld % 8 == 0), "attention: bad gradient row stride");
   a.gl = grad_ld == 0 ? (long)H * kD : grad_ld;
-  a.o = P<const bf16>(o);
+  FDT_CHECK(o32 != 0, "attention: backward needs the forward's fp32 output copy");
+  a.o32 = P<const float>(o32);
   a.dout = P<const bf16>(dout);
   a.lse = P<float>(lse);
   a.delta = P<float>(delta);

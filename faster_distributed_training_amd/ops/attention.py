@@ -20,7 +20,12 @@ from . import _native
 
 
 def attention_reference(q, k, v, mask=None, dropout_p=0.0, mask_value=None, training=True):
-    """q, k, v: (B, L, H, D); mask: (B, L) with 1 = keep.  Returns (B, L, H, D)."""
+    """q, k, v: (B, L, H, D); mask: (B, L) with 1 = keep.  Returns (B, L, H, D).
+
+    A sample whose mask is all zero (true masking) gets the uniform average of V here, because
+    the fill is ``finfo.min`` and not -inf.  The HIP kernels define that case differently:
+    output exactly 0, log-sum-exp -inf, all gradients of the sample exactly 0
+    (``ops/attention_native.py``)."""
     q, k, v = (t.transpose(1, 2) for t in (q, k, v))
     d = q.size(-1)
     scores = torch.matmul(q, k.transpose(-2, -1)) / math.sqrt(d)

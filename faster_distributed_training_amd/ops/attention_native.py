@@ -4,6 +4,15 @@ q, k, v: (B, L, H, 64) bf16 with the head dim contiguous (the strided per-head v
 the Q/K/V projection outputs: no transpose copies).  Output (B, L, H, 64) contiguous.
 Backward recomputes the probabilities from the saved log2-domain log-sum-exp; dropout is
 regenerated from a per-call seed (counter-based hash), so no mask tensor is stored.
+When a gradient is needed the forward also keeps its output before the bf16 rounding (fp32):
+the backward's delta = rowsum(dO * O) is taken from that copy, because in a row whose
+softmax is nearly one-hot the rounding error of O in delta exceeds dQ and dK themselves.
+
+Fully masked rows (every key of a sample masked, true masking): the kernels define the
+output as exactly 0 and the log-sum-exp as -inf, and dq, dk, dv of that sample as exactly 0;
+nothing is NaN.  ``attention_reference`` differs there by construction: it fills with
+``finfo.min``, so its softmax is uniform and it returns the mean of V.  With a finite fill
+value no row is fully masked and the two agree.
 """
 from __future__ import annotations
 
@@ -49,19 +58,22 @@ class FlashAttention(torch.autograd.Function):
         B, L, H, D = q.shape
         out = torch.empty(B, L, H, D, device=q.device, dtype=torch.bfloat16)
         lse = torch.empty(B, H, L, device=q.device, dtype=torch.float32)
+        out32 = (torch.empty(B, L, H, D, device=q.device, dtype=torch.float32)
+                 if any(ctx.needs_input_grad[:3]) else None)
         seed = int(torch.randint(0, 2**62, (1,)).item()) if dropout_p > 0 else 0
         sptr = DEVICE_SEED.data_ptr() if (DEVICE_SEED is not None and dropout_p > 0) else 0
-        nat.attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _strides(q, k, v), out.data_ptr(), lse.data_ptr(),
+        nat.attn_fwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _strides(q, k, v), out.data_ptr(),
+                     0 if out32 is None else out32.data_ptr(), lse.data_ptr(),
                      0 if mask_u8 is None else mask_u8.data_ptr(), B, L, H, float(fill), float(dropout_p), seed,
                      sptr, _native.stream_ptr())
-        ctx.save_for_backward(qkv if packed else q, None if packed else k, None if packed else v, out, lse, mask_u8)
+        ctx.save_for_backward(qkv if packed else q, None if packed else k, None if packed else v, out32, lse, mask_u8)
         ctx.cfg = (float(fill), float(dropout_p), seed, sptr, packed)
         return out
 
     @staticmethod
     def backward(ctx, g):
         nat = _native.native()
-        q, k, v, out, lse, mask_u8 = ctx.saved_tensors
+        q, k, v, out32, lse, mask_u8 = ctx.saved_tensors
         fill, p, seed, sptr, packed = ctx.cfg
         if packed:
             q, k, v = q.unbind(2)
@@ -75,7 +87,7 @@ class FlashAttention(torch.autograd.Function):
             dk = torch.empty_like(dq)
             dv = torch.empty_like(dq)
         delta = torch.empty(B, H, L, device=q.device, dtype=torch.float32)
-        nat.attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _strides(q, k, v), out.data_ptr(), g.data_ptr(),
+        nat.attn_bwd(q.data_ptr(), k.data_ptr(), v.data_ptr(), _strides(q, k, v), out32.data_ptr(), g.data_ptr(),
                      lse.data_ptr(), delta.data_ptr(), 0 if mask_u8 is None else mask_u8.data_ptr(),
                      dq.data_ptr(), dk.data_ptr(), dv.data_ptr(), B, L, H, fill, p, seed, sptr,
                      dq.stride(1) if packed else 0, _native.stream_ptr())
