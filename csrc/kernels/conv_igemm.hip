@@ -79,6 +79,10 @@ static void conv_igemm_impl(uint64_t x, uint64_t x2, uint64_t ps, uint64_t pt, u
   a.wthru = conv_write_through() ? 1 : 0;
   a.dbg = conv_debug_flags();
   a.slot_mask = part ? stat_slot_mask(part_rows, a.nbm) : 0u;
+  // kg 10 (activation-stationary 1x1 loop) never splits K: its nsplit argument carries xn, the
+  // number of column groups per row block
+  const int xn = kg == 10 ? (nsplit < 1 ? 1 : nsplit) : 1;
+  if (kg == 10) nsplit = 1;
   {
     const int nkt = (a.K + BK - 1) / BK;
     if (nsplit < 1 || nkt <= 1) nsplit = 1;
@@ -102,6 +106,13 @@ static void conv_igemm_impl(uint64_t x, uint64_t x2, uint64_t ps, uint64_t pt, u
   if (kg >= 5 && kg <= 8) {  // halo-staged 3x3 stride-1 loop (conv_h3.hip): prologue-free operands, no split-K
     FDT_CHECK(pro == kProNone && a.nsplit == 1, "kg 5-8 (halo 3x3): prologue-free, nsplit 1");
     FDT_CHECK(launch_h3(pro, epi, act, a, BM, BN, kg, st), "kg 5-8 (halo 3x3): unsupported tile / epilogue");
+    return;
+  }
+  if (kg == 10) {  // activation-stationary 1x1 loop (conv_x1.hip)
+    FDT_CHECK(launch_x1(pro, epi, act, a, BM, BN, xn, pure, st),
+              "kg 10 (stationary 1x1): 1x1 stride-1, prologue none / affine (ReLU, none) / fold, epilogue "
+              "STATS / STORE / ADD / ReLU-mask JOINBWD, tile 128x128 | 64x128, K a multiple of 64 within LDS, "
+              "xn dividing Cout / BN");
     return;
   }
   if (kg == 2 && a.nsplit > 1) kg = 1;  // K groups and split-K are alternatives (kg 4: rotated loop, any split)

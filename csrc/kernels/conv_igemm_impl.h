@@ -71,6 +71,18 @@
 // LDS reads and MFMAs (measured 44 % of wave time waiting, 23 % VALU, 10 % MFMA); two waves
 // per SIMD overlap them with no extra global traffic (unlike split-K's fp32 slabs).
 //
+// Activation-stationary form (kg 10, conv_x1.hip): for 1x1 stride-1 convolutions whose output is
+// several column tiles wide and whose K is short (the expanding 1x1 convolutions, the data
+// gradients of the reducing ones), a workgroup owns BM pixels instead of one BM x BN tile: it
+// loads and transforms its BM x K activation rows once, keeps them in LDS, and loops over its
+// column tiles with the weights streamed through an LDS-DMA ring -- the loads, unpack, prologue
+// fma, repack and ds_write that igemm_kernel repeats for each of the Cout/BN column tiles run
+// once.  Same MFMA order and the same conv_epilogue, so bit-identical to igemm_kernel at the
+// same (BM, BN), nsplit 1.  Taken only where a tuned-table entry says "kg": 10 (measured faster
+// under graph replay for that layer) and the launch is in its support set (x1_supported: PURE,
+// prologue none / affine (ReLU or none) / fold, epilogue STATS / STORE / ADD / ReLU-mask
+// JOINBWD, K a multiple of 64 that fits LDS); every other launch of the entry keeps its tile here.
+//
 // Strided convolutions: forward uses the input stride S; the dgrad of a stride-2
 // convolution is split by output parity into 4 dense classes (each its own tap table and
 // output row map: hi = ho*OS + oy), so no MFMA work is spent on structural zeros.
@@ -1130,6 +1142,9 @@ bool launch_cases_infer(int pro, int epi, int act, const ConvArgs& a, int BM, in
 // stages), kg 7 LDS-DMA single stage (two workgroups per CU), kg 8 LDS-DMA two stages, 16 waves
 bool h3_supported(const ConvArgs& a, int BM);
 bool launch_h3(int pro, int epi, int act, const ConvArgs& a, int BM, int BN, int kg, hipStream_t st);
+// activation-stationary 1x1 loop (conv_x1.hip): kg 10, xn column groups per row block
+bool x1_supported(int pro, int epi, int act, const ConvArgs& a, int BM, int BN, int xn, bool pure);
+bool launch_x1(int pro, int epi, int act, const ConvArgs& a, int BM, int BN, int xn, bool pure, hipStream_t st);
 
 }  // namespace conv
 }  // namespace fdt

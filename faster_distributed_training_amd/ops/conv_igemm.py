@@ -293,11 +293,58 @@ def _loop_kg(ent, kgv):
     return 4 if (kgv == 1 and lp == "rot") else kgv
 
 
-def _kg(ent, kg, tile3, ns, K, pro=None):
+# Activation-stationary 1x1 loop (csrc/kernels/conv_x1_impl.h, kg 10): a workgroup transforms its
+# BM x K activation rows once, keeps them as MFMA fragments in registers and loops over its
+# Cout/BN/xn column tiles.  A tuned entry asks for it with "kg": 10 (and "xn": column groups per
+# row block); x1_ok mirrors the native support set (x1_supported), and a launch outside it keeps
+# the entry's tile on the implicit-GEMM kernel -- fwd0 entries are shared with the frozen forward
+# (EPI_NORMACT), dgrad22 entries by the store / add / join-backward epilogues.
+X1_KG = 10
+X1_BN = 128
+# (BM, K) pairs instantiated: the resident fragments fill 128 VGPRs at 128 x 256 = 64 x 512
+X1_BM_OF_K = {64: 128, 128: 128, 256: 128, 512: 64}
+X1_LDS_MAX = 80 * 1024  # two workgroups per CU
+
+
+def x1_lds_bytes(pro, epi, K, bn=X1_BN):
+    """LDS of one kg-10 workgroup: header (prologue parameters, per-wave statistics), the 4-buffer
+    [BN][32] weight ring and the epilogue's staging rows."""
+    nprm = {PRO_FOLD: 3, PRO_AFFINE_ACT: 2}.get(pro, 0)
+    nq = 3 if epi == EPI_JOINBWD else 2
+    hdr = ((nprm * K + 4 * nq * bn) * 4 + 15) & ~15
+    return hdr + 4 * bn * 32 * 2 + 64 * (bn + 4) * 4
+
+
+def x1_ok(pure, pro, epi, act, K, cout, bm, bn, xn=1, relu_mask=True):
+    """Whether this launch is in the support set of the stationary 1x1 kernel.  ``pure``: 1x1,
+    stride 1, no padding; ``act``: the launch's one activation (prologue's or join's);
+    ``relu_mask``: a join backward reads the ReLU bit mask (not the CELU z / o modes)."""
+    combo = ((pro == PRO_NONE and epi == EPI_STATS and act == 0)
+             or (pro == PRO_AFFINE_ACT and epi == EPI_STATS and act in (0, 1))
+             or (pro == PRO_FOLD and epi == EPI_JOINBWD and act == 1 and relu_mask)
+             or (pro == PRO_FOLD and epi in (EPI_ADD, EPI_STORE) and act == 0))
+    if not pure or not combo or bn != X1_BN or X1_BM_OF_K.get(K) != bm:
+        return False
+    if cout % bn or xn < 1 or (cout // bn) % xn:
+        return False
+    return x1_lds_bytes(pro, epi, K, bn) <= X1_LDS_MAX
+
+
+def _is_pure(shp):
+    return shp.k == 1 and shp.stride == 1 and shp.pad == 0
+
+
+def _kg(ent, kg, tile3, ns, K, pro=None, x1=None):
     """K groups of one launch: explicit ``kg``, else the tuned entry's, else 1 (3 = the
-    LDS-DMA ring, prologue-free launches only)."""
+    LDS-DMA ring, prologue-free launches only; 10 = the stationary 1x1 loop -- an entry's
+    "kg": 10 holds only when ``x1``, this launch's x1_ok, does: otherwise the entry's tile
+    runs on the implicit-GEMM kernel; an explicit 10 is passed on and checked natively)."""
+    if kg == X1_KG:
+        return X1_KG
     if kg is None:
         kg = int(ent.get("kg", 1)) if ent else 1
+        if kg == X1_KG:
+            return X1_KG if (x1 and ns == 1) else 1
         if GLDS and pro == PRO_NONE and kg != 2:
             kg = 3
     if kg == 3:
@@ -366,13 +413,15 @@ def stat_slots(nq: int, C: int, device, M: int | None = None) -> torch.Tensor:
 
 
 def conv_fwd(x, wf, shp: ConvShape, s=None, t=None, act=0, alpha=1.0, tile=None, part=None, nsplit=None,
-             fin=None, kg=None, norm=None, res=None, out_act=None):
+             fin=None, kg=None, norm=None, res=None, out_act=None, xn=None, out=None):
     """y = conv(act(x*s+t)) (or conv(x) when s is None and act == 0); returns
     (y [N,Ho,Wo,Cout] bf16, part [STAT_SLOTS,2,Cout] fp32 slots whose row sum is
     (sum y, sum y^2)).  ``part``: a zeroed slot buffer to accumulate into.
     ``fin`` = (fptr, fval): then finalise the batch-norm statistics (stats_finalize
     arguments: gamma beta run_mean run_var nbt s t save_mean save_aux / mode eps momentum
     count) and re-zero the slots.
+    ``xn``: column groups per row block of the stationary 1x1 loop (kg 10; default: the tuned
+    entry's, else 1).  ``out``: the output buffer to write (default: a fresh one).
     ``norm`` = (s, t) fp32 [Cout]: frozen inference -- the conv's own epilogue stores
     out_act(y*s + t (+ ``res``)) (EPI_NORMACT; ``res``: a bf16 tensor of the output's shape,
     ``out_act`` = (act, alpha), default none) and no statistics are taken: no slots, no finalize;
@@ -414,9 +463,18 @@ def conv_fwd(x, wf, shp: ConvShape, s=None, t=None, act=0, alpha=1.0, tile=None,
             # (frozen: the layer keeps its tuned K groups and loop form, only the split factor goes)
             ent = dict(ent or {}, nsplit=nsplit) if frozen else {"nsplit": nsplit}
         ns, slab_p, cnt_p = _splitk_args(ent, M, shp.cout, shp.ntaps * C, bm, bn, bk, x.device)
-        kgv = _kg(ent, kg, (bm, bn, bk), ns, shp.ntaps * C, pro)
+        xn = int(xn if xn is not None else (ent or {}).get("xn", 1))
+        x1 = x1_ok(_is_pure(shp), pro, EPI_NORMACT if frozen else EPI_STATS, int(act), shp.ntaps * C, shp.cout,
+                   bm, bn, xn)
+        kgv = _kg(ent, kg, (bm, bn, bk), ns, shp.ntaps * C, pro, x1)
     _log("fwd", N, H, shp, ent, (bm, bn, bk), ns, kgv)
-    y = torch.empty(N, Ho, Wo, shp.cout, device=x.device, dtype=torch.bfloat16)
+    if kgv == X1_KG:  # (the native nsplit argument carries xn: this kernel never splits K)
+        ns, slab_p, cnt_p = xn, 0, 0
+    if out is None:
+        y = torch.empty(N, Ho, Wo, shp.cout, device=x.device, dtype=torch.bfloat16)
+    else:
+        y = out
+        assert y.dtype == torch.bfloat16 and y.is_contiguous() and tuple(y.shape) == (N, Ho, Wo, shp.cout)
     dh, dw, wt = taps_fwd(shp.k, shp.pad)
     if frozen:
         nat.conv_igemm(x.data_ptr(), 0, 0, 0, 0, wf.data_ptr(), y.data_ptr(), 0, 0,
@@ -480,7 +538,7 @@ def conv_fwd_join(y, r, s, t, s2, t2, wf, shp: ConvShape, jout, jmask=None, tile
 
 def conv_dgrad(g, y, al, be, wd, shp: ConvShape, x_shape, epi=EPI_STORE, out=None, ex=None, es=None, et=None,
                act=0, alpha=1.0, tile=None, part=None, nsplit=None, gs=None, jmask=None, jyb=None, jout=None,
-               coef=None, kg=None, jz=None):
+               coef=None, kg=None, jz=None, xn=None):
     """Data gradient of y = conv(a): dA = conv^T(g*gs + al + be*y)  (gs None: 1).
 
     epi: EPI_STORE -> write dA; EPI_ADD -> out += dA; EPI_ACTBWD -> through the lazy
@@ -497,7 +555,8 @@ def conv_dgrad(g, y, al, be, wd, shp: ConvShape, x_shape, epi=EPI_STORE, out=Non
     the block input).
     ``coef`` = (fptr, fval) with EPI_ACTBWD / EPI_JOINBWD: then turn the statistics into the
     producer units' BN-backward coefficients (stats_bwd_finalize arguments, units A and B:
-    save_mean save_aux gamma alpha beta ggamma gbeta / mode eps count)."""
+    save_mean save_aux gamma alpha beta ggamma gbeta / mode eps count).
+    ``xn``: column groups per row block of the stationary 1x1 loop (kg 10)."""
     nat = _native.native()
     N, Hy, Wy, Cy = g.shape
     assert Cy == shp.cout and g.is_contiguous() and (y is None or y.is_contiguous())
@@ -521,7 +580,10 @@ def conv_dgrad(g, y, al, be, wd, shp: ConvShape, x_shape, epi=EPI_STORE, out=Non
     if tile is None:
         pro = PRO_FOLD if al is not None else PRO_NONE
         e = EPI_STORE if epi in (EPI_ADD, EPI_JOINBWD) else epi
-        ent = tuned(f"dgrad{pro}{e}", N, Hx, shp) or tuned("dgrad", N, Hx, shp)
+        # (an epilogue's own entry first -- the join backward may want another choice than the
+        # plain store -- then the one the three share)
+        ent = ((tuned(f"dgrad{pro}{epi}", N, Hx, shp) if e != epi else None)
+               or tuned(f"dgrad{pro}{e}", N, Hx, shp) or tuned("dgrad", N, Hx, shp))
         tile = tuple(ent["tile"]) if ent else None
     if nsplit is not None:
         ent = {"nsplit": nsplit}
@@ -551,8 +613,13 @@ def conv_dgrad(g, y, al, be, wd, shp: ConvShape, x_shape, epi=EPI_STORE, out=Non
         else:
             bm, bn, bk = _tile3(tile, M, shp.cin)
             ns, slab_p, cnt_p = _splitk_args(ent, M, shp.cin, len(dh) * Cy, bm, bn, bk, g.device)
-            kgv = _kg(ent, kg, (bm, bn, bk), ns, len(dh) * Cy, pro)
+            xnv = int(xn if xn is not None else (ent or {}).get("xn", 1))
+            x1 = x1_ok(_is_pure(shp), pro, epi, int(act) if epi == EPI_JOINBWD else 0, len(dh) * Cy, shp.cin,
+                       bm, bn, xnv, relu_mask=jmask is not None and jz is None)
+            kgv = _kg(ent, kg, (bm, bn, bk), ns, len(dh) * Cy, pro, x1)
         _log("dgrad", N, Hx, shp, ent, (bm, bn, bk), ns, kgv)
+        if kgv == X1_KG:  # (the native nsplit argument carries xn)
+            ns, slab_p, cnt_p = xnv, 0, 0
         assert gs is None or pro == PRO_FOLD, "gs needs the fold prologue (al/be)"
         nat.conv_igemm(g.data_ptr(), _p(y) if pro == PRO_FOLD else 0, _p(al), _p(be), _p(gs), wd.data_ptr(),
                        out.data_ptr(), _p(part) if epi in (EPI_ACTBWD, EPI_JOINBWD) else 0,
