@@ -85,6 +85,17 @@ void mixup_ce_fwd(uint64_t logits, uint64_t ya, uint64_t yb, uint64_t lam, float
                   uint64_t dlam, uint64_t meter, int B, int C, int dt, int labels64, uint64_t stream);
 void mixup_prep(uint64_t y, int b, float lam, uint64_t seed, uint64_t perm, uint64_t yb, uint64_t lam_vec,
                 uint64_t stream);
+// label-smoothed mixup cross entropy (0 <= eps < 1); mixup_ce_fwd stays the unsmoothed kernel
+void mixup_ce_smooth_fwd(uint64_t logits, uint64_t ya, uint64_t yb, uint64_t lam, float lam_s, uint64_t loss,
+                         uint64_t glog, uint64_t dlam, uint64_t meter, int B, int C, int dt, int labels64, float eps,
+                         uint64_t stream);
+// CutMix: box = int32 [b,4] (y0, y1, x0, x1); xdiv = 1 for contiguous NCHW, cp for padded NHWC
+void cutmix_prep(uint64_t y, int b, int H, int W, int bh, int bw, int per_sample, uint64_t seed, uint64_t perm,
+                 uint64_t yb, uint64_t box, uint64_t lam_vec, uint64_t stream);
+void cutmix_fwd(uint64_t x, uint64_t perm, uint64_t box, uint64_t out, int b, long inner, int H, int W, int xdiv,
+                int dt, uint64_t stream);
+void cutmix_bwd(uint64_t g, uint64_t inv, uint64_t box, uint64_t gx, int b, long inner, int H, int W, int xdiv, int dt,
+                uint64_t stream);
 // layernorm.hip
 void layernorm_fwd(uint64_t x, uint64_t a, uint64_t b, uint64_t y, uint64_t mean, uint64_t rstd, long rows, int d,
                    float eps, int dt_x, int dt_y, int dt_w, uint64_t stream);

@@ -1,8 +1,8 @@
 """ResNet / CIFAR-10 and CIFAR-100 training driver (reference ``resnet50_test.py:460-740``; T1, T2, T5).
 
 Per step (all on device, no host synchronisation):
-  batch (device-resident CIFAR + GPU augment) -> mixup (A1) or meta-mixup (A2) ->
-  forward (HIP engine, bf16) -> fused mixup cross-entropy -> backward (DDP buckets
+  batch (device-resident CIFAR + GPU augment) -> mixup (A1), meta-mixup (A2) or CutMix ->
+  forward (HIP engine, bf16) -> fused mixup cross-entropy (label smoothing) -> backward (DDP buckets
   all-reduced on RCCL while backward runs) -> clip-norm coefficient on device ->
   one fused optimizer launch (MADGRAD / SGD / NGD / Adam) -> device-side metrics.
 Per epoch: metric all-reduce (one collective), scheduler step, eval, rank-0
@@ -21,7 +21,8 @@ import torch.nn as nn
 
 from ..data.cifar import DATASETS, DeviceCIFARLoader, augment_order, synthetic_cifar
 from ..models import resnet as resnet_models
-from ..ops.mixup import unit_grad, MetaMixup, mixup_criterion, mixup_criterion_meta, mixup_data
+from ..ops.mixup import (unit_grad, MetaMixup, cutmix_data, mixup_criterion, mixup_criterion_meta,
+                         mixup_cross_entropy, mixup_data)
 from ..ops.resnet_fused import STAGES
 from ..optim.flat_optim import MADGRAD, SGD, Adam, DeviceGradScaler, GradClipper, MirrorMADGRAD
 from ..optim.ngd import NGD
@@ -88,6 +89,10 @@ class ResNetConfig:
     calibrate_batches: int = 0         # > 0: before each evaluation, re-estimate every unit's running statistics
                                        # on this many un-mixed, augmented training batches
     eval_only: bool = False            # with resume: load, (calibrate,) evaluate once; no training
+    cutmix_prob: float = 0.0           # share of the steps that use CutMix instead of input mixup (1: CutMix only)
+    cutmix_alpha: float = 1.0          # Beta(alpha, alpha) for the CutMix box area
+    cutmix_per_sample: bool = False    # a box per sample (default: one box per batch, as the paper)
+    label_smoothing: float = 0.0       # training loss only: the evaluation loss stays unsmoothed
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
@@ -98,6 +103,7 @@ class ResNetConfig:
             self.num_classes = n
         elif self.dataset == "cifar100" and self.num_classes != n:
             raise ValueError(f"dataset 'cifar100' has {n} classes: num_classes={self.num_classes} conflicts")
+        check_mix_config(self.cutmix_prob, self.label_smoothing, self.meta_learning)
 
 
 def check_eval_config(eval_stats: str, fsdp: bool = False, calibrate_batches: int = 0, eval_only: bool = False,
@@ -117,6 +123,18 @@ def check_eval_config(eval_stats: str, fsdp: bool = False, calibrate_batches: in
         raise ValueError("--calibrate_batches re-estimates running statistics: it needs --eval_stats running")
     if eval_only and not resume:
         raise ValueError("--eval_only evaluates a checkpoint: pass --resume")
+
+
+def check_mix_config(cutmix_prob: float = 0.0, label_smoothing: float = 0.0, meta_learning: bool = False):
+    """Refuses inconsistent CutMix / label-smoothing switches (the config's __post_init__ and the
+    CLI call it)."""
+    if not 0.0 <= cutmix_prob <= 1.0:
+        raise ValueError(f"--cutmix_prob must be in [0, 1], not {cutmix_prob}")
+    if not 0.0 <= label_smoothing < 1.0:
+        raise ValueError(f"--label_smoothing must be in [0, 1), not {label_smoothing}")
+    if cutmix_prob > 0 and meta_learning:
+        # meta-mixup owns a learnable per-sample lambda: a pasted box has no use for it
+        raise ValueError("--cutmix_prob > 0 is not supported with --meta_learning")
 
 
 def build_model(cfg: ResNetConfig, device):
@@ -210,6 +228,12 @@ class ResNetTrainer:
         self._build_data()
         self.meter = DeviceMeter(self.device)
         self.logger = JsonlLogger(cfg.log_path)
+        if cfg.cutmix_prob > 0 or cfg.label_smoothing > 0:
+            # (a run without the new switches writes the records it always wrote, and no other)
+            self.logger.log(config=dict(arch=cfg.arch, dataset=cfg.dataset, bs=cfg.bs, alpha=cfg.alpha,
+                                        cutmix_prob=cfg.cutmix_prob, cutmix_alpha=cfg.cutmix_alpha,
+                                        cutmix_per_sample=cfg.cutmix_per_sample,
+                                        label_smoothing=cfg.label_smoothing))
         self.training_acc, self.testing_acc, self.epoch_time = [], [], []
         self.global_step = 0
         self.skipped = torch.zeros((), device=self.device, dtype=torch.int32)  # non-finite steps
@@ -356,6 +380,11 @@ class ResNetTrainer:
         prof.mark("mixup")
         if self.meta is not None:
             x, ya, yb, lam = self.meta(x, y)
+        elif cfg.cutmix_prob > 0 and (cfg.cutmix_prob >= 1 or float(torch.rand(())) < cfg.cutmix_prob):
+            # (the choice comes from the host generator that seed_everything seeded per rank and
+            # mixup_data draws from -- only when 0 < cutmix_prob < 1, so other runs draw what they
+            # drew; lam: the per-sample fp32 vector of the clipped boxes, on the device)
+            x, ya, yb, lam = cutmix_data(x, y, cfg.cutmix_alpha, per_sample=cfg.cutmix_per_sample)
         else:
             x, ya, yb, lam = mixup_data(x, y, cfg.alpha)
         prof.mark("forward")
@@ -363,9 +392,12 @@ class ResNetTrainer:
             out = self.model(x)
             prof.mark("loss")
             if self.meta is not None:
-                loss = mixup_criterion_meta(None, out, ya, yb, lam, faithful=cfg.faithful, meter=self.meter)
+                loss = mixup_criterion_meta(None, out, ya, yb, lam, faithful=cfg.faithful, meter=self.meter,
+                                            label_smoothing=cfg.label_smoothing)
+            elif isinstance(lam, torch.Tensor):  # CutMix: a lambda per sample
+                loss = mixup_cross_entropy(out, ya, yb, lam, meter=self.meter, label_smoothing=cfg.label_smoothing)
             else:
-                loss = mixup_criterion(None, out, ya, yb, lam, meter=self.meter)
+                loss = mixup_criterion(None, out, ya, yb, lam, meter=self.meter, label_smoothing=cfg.label_smoothing)
         prof.mark("backward")
         if self.scaler.enabled or loss.dtype != torch.float32 or loss.dim() != 0:
             self.scaler.scale_loss(loss).backward()

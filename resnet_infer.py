@@ -13,6 +13,13 @@ and the data set switch:
 
   --dataset {cifar10,cifar100}   cifar100: 100 fine labels, checkpoints resnet_cifar100_*.pth, top-5 in the evaluation
 
+and the training-recipe switches:
+
+  --cutmix_prob P                share of the steps that use CutMix instead of input mixup (1: CutMix only)
+  --cutmix_alpha A               Beta(A, A) for the CutMix box area (default 1)
+  --cutmix_per_sample            a box per sample (default: one box per batch)
+  --label_smoothing E            smoothing of the training loss, 0 <= E < 1 (the evaluation loss stays unsmoothed)
+
 Without the new switches it behaves exactly like ``resnet50_test.py``.
 
 Examples:
@@ -20,6 +27,7 @@ Examples:
     python resnet_infer.py --eval_stats running --resume --eval_only --bs 1
     python resnet_infer.py --eval_stats running --calibrate_batches 8 --resume --eval_only
     python resnet_infer.py --dataset cifar100 --synthetic --bs 256 --epoch 1
+    python resnet_infer.py --dataset cifar100 --cutmix_prob 0.5 --label_smoothing 0.1
 """
 from __future__ import annotations
 
@@ -46,15 +54,22 @@ def parse(argv=None):
     p.add_argument("--dataset", default="cifar10", choices=["cifar10", "cifar100"],
                    help="cifar100: the 100 fine labels, a 100-class head, checkpoints in resnet_cifar100_*.pth, "
                         "top-5 accuracy in the evaluation")
+    p.add_argument("--cutmix_prob", default=0.0, type=float,
+                   help="share of the training steps that use CutMix instead of input mixup (1: CutMix only)")
+    p.add_argument("--cutmix_alpha", default=1.0, type=float, help="Beta(alpha, alpha) for the CutMix box area")
+    p.add_argument("--cutmix_per_sample", action="store_true", help="a CutMix box per sample (default: one per batch)")
+    p.add_argument("--label_smoothing", default=0.0, type=float,
+                   help="label smoothing of the training loss, in [0, 1); the evaluation loss stays unsmoothed")
     argv = list(sys.argv[1:] if argv is None else argv)
     if "-h" in argv or "--help" in argv:
         p.print_help()
         print()
     a, rest = p.parse_known_args(argv)
     base = resnet50_test.parse(rest)
-    from faster_distributed_training_amd.train.resnet_trainer import check_eval_config
+    from faster_distributed_training_amd.train.resnet_trainer import check_eval_config, check_mix_config
     try:
         check_eval_config(a.eval_stats, base.fsdp, a.calibrate_batches, a.eval_only, base.resume)
+        check_mix_config(a.cutmix_prob, a.label_smoothing, base.meta_learning)
     except ValueError as e:
         p.error(str(e))
     return a, base
@@ -64,7 +79,9 @@ def config_from_args(a, base):
     # (num_classes=None: the data set decides)
     return dataclasses.replace(resnet50_test.config_from_args(base), eval_stats=a.eval_stats,
                                calibrate_batches=a.calibrate_batches, eval_only=a.eval_only,
-                               dataset=a.dataset, num_classes=None)
+                               dataset=a.dataset, num_classes=None, cutmix_prob=a.cutmix_prob,
+                               cutmix_alpha=a.cutmix_alpha, cutmix_per_sample=a.cutmix_per_sample,
+                               label_smoothing=a.label_smoothing)
 
 
 def main(argv=None):
