@@ -1,7 +1,8 @@
 // LayerNorm with the reference's numerics (transformer.py:230-242):
 //     y = a * (x - mean) / (std_unbiased + eps) + b
 // One row per wave64; each lane owns E = d/64 elements held in registers, so x is read
-// once (forward) / x and dy once (backward).  Statistics in fp32, two-pass in registers.
+// once (forward) / x and dy once (backward).  Statistics two-pass in registers: the row sum
+// in fp64 (a correctly rounded fp32 mean), the variance in fp32.
 // Backward (r = 1/(std+eps), ga = a*dy, S1 = sum ga, S2 = sum ga*(x-mean)):
 //     dx = r*(ga - S1/d) - r^2 * S2 * (x-mean) / ((d-1)*std)
 // plus per-block partials of dgamma = sum dy*z and dbeta = sum dy (no atomics).
@@ -45,9 +46,13 @@ __global__ __launch_bounds__(64 * kLnWaves) void layernorm_fwd_kernel(const TX* 
   if (row >= rows) return;
   float v[E];
   ln_load<E>(x + row * d, d, lane, v);
-  float s = 0.f;
-  _Pragma("unroll") for (int k = 0; k < E; ++k) s += v[k];
-  const float mean = wave_sum(s) / (float)d;
+  // The row sum is taken in fp64 (E adds per lane, nothing next to the row's HBM traffic), so the
+  // mean is the fp32 number nearest to the exact one.  An fp32 sum of a row with |mean| >> std is
+  // off by a few ulp of the mean, and y by that many ulp times |mean| / std: 5e-4 of its row norm
+  // at mean 100, std 0.01, several times the error of the fp32 PyTorch formula.
+  double s = 0.0;
+  _Pragma("unroll") for (int k = 0; k < E; ++k) s += (double)v[k];
+  const float mean = (float)(wave_sum(s) / (double)d);
   float q = 0.f;
   _Pragma("unroll") for (int k = 0; k < E; ++k) { float c = v[k] - mean; q = fmaf(c, c, q); }
   const float var = wave_sum(q) / (float)(d - 1);
@@ -140,11 +145,15 @@ __global__ __launch_bounds__(64 * kLnWaves) void layernorm_bwd_kernel(const TG* 
   switch (ev) {                                                    \
     case 1: { constexpr int E = 1; __VA_ARGS__; break; }           \
     case 2: { constexpr int E = 2; __VA_ARGS__; break; }           \
+    case 3: { constexpr int E = 3; __VA_ARGS__; break; }           \
     case 4: { constexpr int E = 4; __VA_ARGS__; break; }           \
+    case 6: { constexpr int E = 6; __VA_ARGS__; break; }           \
     case 8: { constexpr int E = 8; __VA_ARGS__; break; }           \
+    case 12: { constexpr int E = 12; __VA_ARGS__; break; }         \
     case 16: { constexpr int E = 16; __VA_ARGS__; break; }         \
+    case 24: { constexpr int E = 24; __VA_ARGS__; break; }         \
     case 32: { constexpr int E = 32; __VA_ARGS__; break; }         \
-    default: throw std::runtime_error("layernorm: d must be 64*{1,2,4,8,16,32}"); \
+    default: throw std::runtime_error("layernorm: d must be 64*{1,2,3,4,6,8,12,16,24,32} (ops/layernorm.py NATIVE_WIDTHS)"); \
   }
 
 void layernorm_fwd(uint64_t x, uint64_t a, uint64_t b, uint64_t y, uint64_t mean, uint64_t rstd, long rows, int d,

@@ -16,6 +16,10 @@ from . import _native
 
 DT = {torch.float32: 0, torch.bfloat16: 1, torch.float16: 2}
 
+# The widths layernorm.hip instantiates (DISPATCH_E: d / 64 elements per lane); any other
+# width takes ``layer_norm_reference``.  The kernel throws for a width missing there.
+NATIVE_WIDTHS = (64, 128, 192, 256, 384, 512, 768, 1024, 1536, 2048)
+
 
 def layer_norm_reference(x, a, b, eps=1e-6):
     mean = x.mean(-1, keepdim=True)
@@ -105,7 +109,7 @@ class _LayerNormNative(torch.autograd.Function):
 
 def layer_norm_unbiased(x, a, b, eps=1e-6, res: ResidualGrad | None = None):
     """``res``: the residual block's skip-gradient hand-off (see ResidualGrad)."""
-    if (_native.use_native(x) and x.shape[-1] % 64 == 0 and 64 <= x.shape[-1] <= 2048
+    if (_native.use_native(x) and x.shape[-1] in NATIVE_WIDTHS
             and x.dtype in DT and a.dtype == torch.float32):
         out_dtype = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
         return _LayerNormNative.apply(x, a, b, eps, out_dtype, res)

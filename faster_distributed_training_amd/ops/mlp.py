@@ -3,7 +3,7 @@
 
 The reference backward runs a per-element Python loop with a host sync per element
 (survey Q6) and averages the bias gradients over the batch (Q5).  Here the ReLU mask,
-bias add and bias-gradient reduction are fused: forward is ``GEMM -> (bias+ReLU) ->
+bias add and bias-gradient reduction are fused: forward is ``GEMM(+bias) -> ReLU ->
 GEMM(+bias)``; backward is ``GEMM -> (mask + column-sum) -> GEMM x2``.  On GPU the
 elementwise+reduction steps are one HIP kernel each (``csrc/kernels/mlp.hip``);
 ``bias_grad_mean=True`` reproduces the reference's 1/B bias gradients.
@@ -25,22 +25,19 @@ class FusedMLPFunction(torch.autograd.Function):
         dt = torch.get_autocast_dtype(X.device.type) if torch.is_autocast_enabled(X.device.type) else X.dtype
         x2 = _flat2(X).to(dt)
         w1, w2 = W1.to(dt), W2.to(dt)
-        pre = x2 @ w1.t()
+        # both biases ride in their GEMM (one rounding of product + bias, as F.linear does): added
+        # in a separate pass to the already rounded bf16 / fp16 product, they cost a second
+        # rounding, 2-4x the row error of the plain composition (tests/test_pointwise_edges.py)
+        pre = x2 @ w1.t() if b1 is None else torch.addmm(b1.to(dt).reshape(-1), x2, w1.t())
         nat = _native.load() if _native.use_native(X) else None
         if nat is not None and hasattr(nat, "bias_relu_fwd") and pre.is_contiguous():
-            # one pass: pre += b1 (in place, kept for the ReLU mask); act = relu(pre)
-            act = torch.empty_like(pre)
-            b1f = b1.float().contiguous() if b1 is not None else None
-            nat.bias_relu_fwd(pre.data_ptr(), _native.ptr(b1f), act.data_ptr(),
+            act = torch.empty_like(pre)  # act = relu(pre); pre is kept for the ReLU mask
+            nat.bias_relu_fwd(pre.data_ptr(), 0, act.data_ptr(),
                               pre.shape[0], pre.shape[1], 1 if dt == torch.bfloat16 else (2 if dt == torch.float16 else 0),
                               _native.stream_ptr())
         else:
-            if b1 is not None:
-                pre = pre + b1.to(dt)
             act = torch.relu(pre)
-        out = act @ w2.t()
-        if b2 is not None:
-            out = out + b2.to(dt)
+        out = act @ w2.t() if b2 is None else torch.addmm(b2.to(dt).reshape(-1), act, w2.t())
         ctx.save_for_backward(x2, w1, w2, pre, act)
         ctx.has_b = (b1 is not None, b2 is not None)
         ctx.mean = bias_grad_mean
