@@ -143,6 +143,12 @@ void conv_wgrad(uint64_t g, uint64_t y, uint64_t al, uint64_t be, uint64_t gs, u
                 uint64_t stream);
 void wgrad_reduce(uint64_t slab, uint64_t out, int nsplit, int Cout, int Cin, int ntaps, int Cxp, int accumulate,
                   uint64_t stream);
+// conv_bwd_pair.hip: data + weight gradient of an expanding 1x1 convolution in one pass
+void conv_bwd_pair(uint64_t g, uint64_t y, uint64_t al, uint64_t be, uint64_t gs, uint64_t wd, uint64_t x, uint64_t xs,
+                   uint64_t xt, uint64_t es, uint64_t et, uint64_t dx, uint64_t part, int part_rows, uint64_t dw,
+                   uint64_t slab, long M, int Cin, int Cout, int epi, int act, int wgs, int accumulate,
+                   uint64_t stream);
+bool conv_bwd_pair_supported(int Cin, int Cout, int epi, int act, int xaff);
 void pack_weights(const std::vector<uint64_t>& src, const std::vector<uint64_t>& wf, const std::vector<uint64_t>& wd,
                   const std::vector<int>& cout, const std::vector<int>& cin, const std::vector<int>& cxp,
                   const std::vector<int>& ntaps, uint64_t stream);

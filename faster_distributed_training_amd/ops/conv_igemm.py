@@ -769,6 +769,79 @@ def conv_wgrad(g, y, al, be, x, shp: ConvShape, out, xs=None, xt=None, act=0, al
     return out
 
 
+# Fused backward of the expanding 1x1 convolutions (csrc/kernels/conv_bwd_pair.hip): data and
+# weight gradient in one pass over g, y and x instead of a conv_dgrad + conv_wgrad pair that
+# each stream and fold g and y.  Taken by the engine where conv_tuned.json has a "bwdpair" entry
+# for the layer and bwd_pair_ok holds; FDT_BWD_PAIR=0 keeps the two launches (A/B).
+BWD_PAIR = os.environ.get("FDT_BWD_PAIR", "1") != "0"
+BWD_PAIR_WGS = 256  # persistent workgroups: one per CU
+BWD_PAIR_PX = 128   # pixels per chunk
+_BWD_PAIR_SLAB: dict = {}
+
+
+def bwd_pair_ok(shp: "ConvShape", epi, act, fold=True, xaff=None) -> bool:
+    """Whether the fused data + weight gradient is instantiated for this launch: a PURE
+    64 -> 256 convolution with the BN-backward fold, and either the ACTBWD epilogue through a
+    ReLU (the weight gradient's input transform relu(x*xs+xt) set) or the plain store with an
+    identity input.  ``xaff``: the weight gradient has an input transform (default: as the
+    epilogue implies)."""
+    if xaff is None:
+        xaff = epi == EPI_ACTBWD
+    if not _is_pure(shp) or not fold or shp.cin != 64 or shp.cout != 4 * shp.cin or shp.cxp != shp.cin:
+        return False
+    if epi == EPI_ACTBWD:
+        return int(act) == 1 and bool(xaff)
+    return epi == EPI_STORE and int(act) == 0 and not xaff
+
+
+def bwd_pair_entry(batch: int, h: int, shp: "ConvShape", epi, act, fold=True, xaff=None):
+    """The layer's "bwdpair" table entry ({"tile": [chunk pixels, Cin, K tile], "wgs": workgroups})
+    if the fused launch is to run there, else None."""
+    if not BWD_PAIR or not bwd_pair_ok(shp, epi, act, fold, xaff):
+        return None
+    return tuned("bwdpair", batch, h, shp)
+
+
+def conv_bwd_pair(g, y, al, be, wd, x, shp: ConvShape, dw, epi=EPI_STORE, xs=None, xt=None, es=None, et=None, act=0,
+                  part=None, gs=None, accumulate=False, coef=None, wgs=None, out=None):
+    """conv_dgrad(g, y, al, be, wd, ..., epi, ex=x, es, et, act, part, gs, coef) and
+    conv_wgrad(g, y, al, be, x, shp, dw, xs, xt, act, accumulate, gs) of a PURE expanding
+    convolution in one launch (bwd_pair_ok).  Returns (dx, part or None).  ``wgs``: the most
+    workgroups to use (each owns ceil(chunks / wgs) 128-pixel chunks)."""
+    nat = _native.native()
+    N, H, W, Cy = g.shape
+    assert bwd_pair_ok(shp, epi, act, al is not None, xs is not None), "conv_bwd_pair: unsupported launch"
+    assert Cy == shp.cout and tuple(x.shape) == (N, H, W, shp.cin) and tuple(y.shape) == tuple(g.shape)
+    assert g.is_contiguous() and y.is_contiguous() and x.is_contiguous() and dw.is_contiguous()
+    assert g.dtype == y.dtype == x.dtype == torch.bfloat16 and dw.dtype == torch.float32
+    assert dw.numel() == shp.cout * shp.cin
+    M = N * H * W
+    if out is None:
+        out = torch.empty(N, H, W, shp.cin, device=g.device, dtype=torch.bfloat16)
+    if epi == EPI_ACTBWD and part is None:
+        part = stat_slots(2, shp.cin, g.device, M)
+    wgs = int(wgs or BWD_PAIR_WGS)
+    slab = None
+    if _native.deterministic():
+        # (sized for the default grid in the eager warm-up step; graph replay reuses it)
+        need = max(wgs, BWD_PAIR_WGS) * shp.cout * shp.cin
+        slab = _BWD_PAIR_SLAB.get(g.device)
+        if slab is None or slab.numel() < need:
+            slab = _BWD_PAIR_SLAB[g.device] = torch.empty(need, device=g.device, dtype=torch.float32)
+    chunks = -(-M // BWD_PAIR_PX)
+    cpw = -(-chunks // wgs)
+    _log("bwdpair", N, H, shp, tuned("bwdpair", N, H, shp), (BWD_PAIR_PX, shp.cin, 64), -(-chunks // cpw), 11)
+    actbwd = epi == EPI_ACTBWD
+    nat.conv_bwd_pair(g.data_ptr(), y.data_ptr(), al.data_ptr(), be.data_ptr(), _p(gs), wd.data_ptr(), x.data_ptr(),
+                      _p(xs), _p(xt), _p(es) if actbwd else 0, _p(et) if actbwd else 0, out.data_ptr(),
+                      _p(part) if actbwd else 0, part.shape[0] if actbwd else 0, dw.data_ptr(), _p(slab), M,
+                      shp.cin, shp.cout, int(epi), int(act), wgs, int(accumulate), _sp())
+    if coef is not None:
+        assert actbwd
+        _finalize_standalone(nat, 2, part, 2, shp.cin, coef[0], coef[1])
+    return out, (part if actbwd else None)
+
+
 def pack_weights(entries):
     """entries: iterable of (w fp32 OIHW, wf bf16 or None, wd bf16 or None, ConvShape); one
     launch (a None layout is skipped)."""

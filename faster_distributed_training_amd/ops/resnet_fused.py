@@ -522,6 +522,17 @@ def wgrad_into(u: Unit, g, y, al, be, x, xs, xt, act, gs=None):
     grad_ready(u.w)
 
 
+def bwd_pair_into(u: Unit, g, y, al, be, x, xs, xt, epi, act, part=None, gs=None, coef=None, ent=None):
+    """Data gradient + wgrad_into of a PURE expanding unit in one launch (ci.conv_bwd_pair);
+    ``ent``: the layer's "bwdpair" table entry (its "wgs": the workgroups to use)."""
+    if u.w.grad is None:
+        u.w.grad = torch.zeros_like(u.w)
+    dx, _ = ci.conv_bwd_pair(g, y, al, be, u.wd, x, u.shp, u.w.grad, epi=epi, xs=xs, xt=xt, es=xs, et=xt, act=act,
+                             part=part, gs=gs, accumulate=True, coef=coef, wgs=(ent or {}).get("wgs"))
+    grad_ready(u.w)
+    return dx
+
+
 def _rows(t):
     return t.numel() // t.shape[-1]
 
@@ -691,9 +702,15 @@ class ResNetBodyFn(torch.autograd.Function):
             if sc is not None:
                 u = b.shortcut
                 als, bes = coef_sc
-                g_x, _ = ci.conv_dgrad(gpre, sc[0], als, bes, u.wd, u.shp, tuple(x_in.shape), epi=ci.EPI_STORE,
-                                       gs=sc[1])
-                wgrad_into(u, gpre, sc[0], als, bes, x_in, None, None, (ACT_NONE, 1.0), gs=sc[1])
+                if (tuple(x_in.shape[:3]) == tuple(gpre.shape[:3]) and x_in.is_contiguous()
+                        and (bpe := ci.bwd_pair_entry(x_in.shape[0], x_in.shape[1], u.shp, ci.EPI_STORE, ACT_NONE,
+                                                      als is not None, False))):
+                    g_x = bwd_pair_into(u, gpre, sc[0], als, bes, x_in, None, None, ci.EPI_STORE, ACT_NONE, gs=sc[1],
+                                        ent=bpe)
+                else:
+                    g_x, _ = ci.conv_dgrad(gpre, sc[0], als, bes, u.wd, u.shp, tuple(x_in.shape), epi=ci.EPI_STORE,
+                                           gs=sc[1])
+                    wgrad_into(u, gpre, sc[0], als, bes, x_in, None, None, (ACT_NONE, 1.0), gs=sc[1])
             else:
                 g_x = gpre  # identity: the x_in gradient accumulates onto g_pre in place
             # the block whose output is x_in: its join backward runs in the epilogue of the
@@ -725,6 +742,11 @@ class ResNetBodyFn(torch.autograd.Function):
                         wgrad_into(u, gf, None, None, None, a_in if a_in is not None else yp,
                                    None if a_in is not None else sp_, None if a_in is not None else tp,
                                    (ACT_NONE, 1.0) if a_in is not None else actp)
+                    elif (tuple(yp.shape[:3]) == tuple(g_cur.shape[:3])
+                          and (bpe := ci.bwd_pair_entry(yp.shape[0], yp.shape[1], u.shp, ci.EPI_ACTBWD, actp[0],
+                                                        al is not None, True))):
+                        g_prev = bwd_pair_into(u, g_cur, y, al, be, yp, sp_, tp, ci.EPI_ACTBWD, actp[0], part=pp,
+                                               gs=gs_cur, coef=cf, ent=bpe)
                     else:
                         g_prev, _ = ci.conv_dgrad(g_cur, y, al, be, u.wd, u.shp, tuple(yp.shape),
                                                   epi=ci.EPI_ACTBWD, ex=yp, es=sp_, et=tp, act=actp[0],
