@@ -62,6 +62,23 @@ void adam_step(uint64_t p, uint64_t g, uint64_t m, uint64_t v, uint64_t shadow, 
                float eps, float wd, int adamw, long step, uint64_t kskip, uint64_t gsc, uint64_t found_inf,
                int zero_grad, uint64_t stream);
 void cast_bf16(uint64_t x, uint64_t y, long n, uint64_t stream);
+// layer-wise adaptive rates (optim_layerwise.hip): LARS / LAMB over a tile table of the flat
+// buffer's slots.  tiles = int32 [ntiles, 4] rows {slot, first element, element count, first
+// tile of the slot}; slots = int32 [nslots, 4] rows {first tile, tile count, adapted, decayed};
+// part = fp32 [ntiles, 2]; trust = fp32 [nslots]; norms = fp32 [nslots, 2]
+int layer_tile();
+void slot_sumsq(uint64_t a, uint64_t b, uint64_t tiles, int ntiles, uint64_t part, uint64_t found_inf, uint64_t stream);
+void slot_finalize(uint64_t part, uint64_t slots, int nslots, int lamb, double eta, double wd, double eps, uint64_t gsc,
+                   uint64_t found_inf, uint64_t trust, uint64_t norms, uint64_t stream);
+void lars_apply(uint64_t p, uint64_t g, uint64_t buf, uint64_t shadow, uint64_t tiles, int ntiles, uint64_t slots,
+                uint64_t trust, float lr, float momentum, float dampening, float wd, int nesterov, int first,
+                uint64_t gsc, uint64_t found_inf, int zero_grad, uint64_t stream);
+void lamb_moments(uint64_t p, uint64_t g, uint64_t m, uint64_t v, uint64_t tiles, int ntiles, uint64_t slots,
+                  uint64_t part, float b1, float b2, float eps, float wd, long step, uint64_t kskip, uint64_t gsc,
+                  uint64_t found_inf, uint64_t stream);
+void lamb_apply(uint64_t p, uint64_t g, uint64_t m, uint64_t v, uint64_t shadow, uint64_t tiles, int ntiles,
+                uint64_t slots, uint64_t trust, float lr, float b1, float b2, float eps, float wd, long step,
+                uint64_t kskip, uint64_t found_inf, int zero_grad, uint64_t stream);
 // fused optimizer step + conv weight repack (optim_pack.hip): tab = int64 [ntab, 8] entries
 // (flat offset, wf, wd, Cout, Cin, Cxp, ntaps, first block), rr = int64 [nrr, 3] rest ranges
 void madgrad_pack_step(uint64_t p, uint64_t g, uint64_t gss, uint64_t s, uint64_t x0, uint64_t shadow, long n,

@@ -6,6 +6,8 @@ reference uses, survey A10) whose ``step`` is ONE HIP launch over the whole mode
 grad * clip-coefficient (device scalar) -> found-inf skip (device flag) -> weight decay
 -> update -> bf16 shadow write -> grad zeroing (``csrc/kernels/optim.hip``).
 The CPU path runs the same math with torch ops (also the kernel-test oracle).
+LARS and LAMB add a per-slot trust ratio: three launches over a tile table of the slots
+(``csrc/kernels/optim_layerwise.hip``), their CPU path a per-slot loop over ``flat.slots``.
 
 Reference update rules:
 * SGD / momentum / dampening / nesterov: ``ngd_optimizer.py:478-506`` (the NGD tail) and
@@ -349,6 +351,245 @@ class Adam(FlatOptimizer):
         m.mul_(b1).add_(gr, alpha=1 - b1)
         v.mul_(b2).addcmul_(gr, gr, value=1 - b2)
         p.addcdiv_(m / (1 - b1 ** step), (v / (1 - b2 ** step)).sqrt_().add_(g["eps"]), value=-g["lr"])
+        self._finish_cpu()
+
+
+# ------------------------------------------------------------------ layer-wise adaptive rates
+def _layer_tile() -> int:
+    """Elements per tile of the slot tile table: the native module's kLayerTile
+    (csrc/kernels/optim_layerwise.hip) wherever it is built; without it only the CPU paths run,
+    which cut no tiles, and the kernel's value at the time of writing stands in."""
+    m = _native.load()
+    return int(m.layer_tile()) if m is not None and hasattr(m, "layer_tile") else 4096
+
+
+LAYER_TILE = _layer_tile()
+
+LAYERWISE = ("lars", "lamb")
+
+
+def check_layerwise_config(optimizer: str, fsdp: bool = False):
+    """Refuses LARS / LAMB under --fsdp (resnet_infer.py and transformer_train.py call it when they
+    parse their arguments, the trainers before they set anything up)."""
+    if optimizer in LAYERWISE and fsdp:
+        raise ValueError(f"--optimizer {optimizer} is not supported with --fsdp: an FSDP shard view holds no whole "
+                         "parameter slots, so the per-slot norms of the trust ratio would need a collective "
+                         "(plain data parallel works: every rank steps on the all-reduced gradients)")
+
+
+def build_tile_table(flat, tile: int = LAYER_TILE, exclude_1d: bool = True, adapt: bool = True):
+    """The slot tile table of a flat layout, as two int32 arrays (host tensors).
+
+    ``tiles [ntiles, 4]``: {slot index, first element, element count, first tile of the slot} --
+    every slot cut into tiles of at most ``tile`` elements, covering exactly its ``numel``
+    elements (the alignment padding belongs to no tile).  ``slots [nslots, 4]``: {first tile,
+    tile count, adapted, decayed}.  A slot is adapted (trust ratio) and decayed iff its parameter
+    has more than one dimension, or always with ``exclude_1d=False``; ``adapt=False`` switches
+    the trust ratio off everywhere and keeps the decay on every slot (plain SGD / AdamW).
+    Only ``(offset, numel, shape)`` enter, so ``FlatParams(partition=W)`` layouts work alike."""
+    from ..utils.flat import ALIGN
+    if flat.numel >= 2 ** 31:
+        raise ValueError("the tile table indexes elements with int32: flat buffer too large")
+    rows, srows, t = [], [], 0
+    for si, sl in enumerate(flat.slots):
+        n, off = int(sl.numel), int(sl.offset)
+        if off % ALIGN or off < 0 or off + (n + ALIGN - 1) // ALIGN * ALIGN > flat.numel:
+            raise ValueError(f"slot {sl.name!r}: offset {off} / numel {n} is not an aligned range of the flat buffer")
+        nt = (n + tile - 1) // tile
+        first = torch.arange(nt, dtype=torch.int64) * tile
+        rows.append(torch.stack([torch.full_like(first, si), off + first, (n - first).clamp(max=tile),
+                                 torch.full_like(first, t)], 1))
+        multi = len(sl.shape) > 1 or not exclude_1d
+        srows.append((t, nt, int(adapt and multi), int(multi or not adapt)))
+        t += nt
+    tiles = torch.cat(rows).to(torch.int32) if rows else torch.zeros(0, 4, dtype=torch.int32)
+    slots = torch.tensor(srows, dtype=torch.int32).reshape(-1, 4)
+    return tiles.contiguous(), slots.contiguous()
+
+
+class LayerwiseOptimizer(FlatOptimizer):
+    """Shared part of LARS and LAMB: the slot tile table, the per-slot buffers and the trust
+    ratio of the last step (``trust``: device tensor ``[nslots]``, not optimizer state).
+
+    The fused update-and-pack path (``optim_pack.hip``) is not used: ``FlatOptimizer.step``
+    invalidates the engine's packed conv weights after every step here (``_packed`` stays
+    false), so the engine repacks them in its next forward."""
+
+    def __init__(self, flat, defaults, **kw):
+        if not hasattr(flat, "slots"):
+            raise ValueError(f"{type(self).__name__} needs whole parameter slots (a FlatParams buffer, not a shard view)")
+        super().__init__(flat, defaults, **kw)
+        self._table_key = None
+        self._tables()
+
+    def _adapt(self) -> bool:
+        return True
+
+    def _tables(self):
+        """Device tile / slot tables and per-slot buffers; rebuilt when the slot table (or a
+        switch that decides the per-slot flags) changes."""
+        g = self.group
+        key = (bool(g["exclude_1d"]), self._adapt(), tuple((s.offset, s.numel) for s in self.flat.slots))
+        if key != self._table_key:
+            tiles, slots = build_tile_table(self.flat, LAYER_TILE, exclude_1d=key[0], adapt=key[1])
+            dev = self.flat.device
+            self.tiles, self.slot_rows = tiles.to(dev), slots.to(dev)
+            self._slot_host = slots
+            self.ntiles, self.nslots = tiles.shape[0], slots.shape[0]
+            self.part = torch.zeros(max(self.ntiles, 1), 2, device=dev, dtype=torch.float32)
+            self.trust = torch.ones(self.nslots, device=dev, dtype=torch.float32)
+            self.norms = torch.zeros(self.nslots, 2, device=dev, dtype=torch.float32)  # diagnostics: |p|, c|g| or |u|
+            self._adapted = torch.nonzero(slots[:, 2]).reshape(-1).to(dev)
+            self._table_key = key
+        return self.tiles, self.slot_rows
+
+    def trust_summary(self):
+        """{min, med, max} of the last step's trust ratios over the adapted slots, or None when
+        no slot is adapted.  The only call here that synchronises with the device."""
+        if self._adapted.numel() == 0:
+            return None
+        t = self.trust[self._adapted]
+        lo, med, hi = torch.stack([t.min(), t.median(), t.max()]).tolist()
+        return {"min": lo, "med": med, "max": hi}
+
+    def _slot_views(self, sl, *bufs):
+        return [b[sl.offset:sl.offset + sl.numel] for b in bufs]
+
+
+class LARS(LayerwiseOptimizer):
+    """SGD with momentum and a layer-wise trust ratio (You et al. 2017).  Per slot s, with the
+    clip coefficient c:  wn = |p_s|, gn = c |g_s|,
+    q_s = eta wn / (gn + wd_s wn + eps) if the slot is adapted and wn, gn > 0, else 1;
+    d = g (q_s c) + (q_s wd_s) p  [= q_s (c g + wd_s p)];  then SGD's momentum / nesterov step.
+    1-D slots (biases, norm scales) are excluded by default: q = 1 and no decay.  ``eta <= 0``
+    switches the trust ratio off (q = 1 everywhere, decay on every slot): plain SGD, bitwise.
+
+    Three launches per step (``optim_layerwise.hip``): slot_sumsq, slot_finalize, lars_apply; no
+    host sync.  The fused update-and-pack path is not used (see ``LayerwiseOptimizer``)."""
+
+    def __init__(self, flat, lr=0.1, momentum=0.9, dampening=0.0, weight_decay=0.0, nesterov=False, eta=1e-3, eps=1e-8,
+                 exclude_1d=True, **kw):
+        if nesterov and (momentum <= 0 or dampening != 0):
+            raise ValueError("Nesterov momentum requires a momentum and zero dampening")
+        super().__init__(flat, dict(lr=lr, momentum=momentum, dampening=dampening, weight_decay=weight_decay,
+                                    nesterov=nesterov, eta=eta, eps=eps, exclude_1d=exclude_1d), **kw)
+
+    def _adapt(self):
+        return self.group["eta"] > 0
+
+    def _step(self, grad_scale, found_inf):
+        g = self.group
+        flat = self.flat
+        tiles, slot_rows = self._tables()
+        buf = self._state_buf("momentum_buffer") if g["momentum"] != 0 else None
+        first = int(self.state["__flat__"].get("initialized", 0) == 0) if buf is not None else 0
+        wd = float(g["weight_decay"])
+        if self._native:
+            nat, sp = _native.native(), _sp()
+            nat.slot_sumsq(flat.data.data_ptr(), flat.grad.data_ptr(), tiles.data_ptr(), self.ntiles,
+                           self.part.data_ptr(), _p(found_inf), sp)
+            nat.slot_finalize(self.part.data_ptr(), slot_rows.data_ptr(), self.nslots, 0, float(g["eta"]), wd,
+                              float(g["eps"]), _p(grad_scale), _p(found_inf), self.trust.data_ptr(),
+                              self.norms.data_ptr(), sp)
+            nat.lars_apply(flat.data.data_ptr(), flat.grad.data_ptr(), _p(buf), _p(flat.shadow), tiles.data_ptr(),
+                           self.ntiles, slot_rows.data_ptr(), self.trust.data_ptr(), float(g["lr"]),
+                           float(g["momentum"]), float(g["dampening"]), wd, int(g["nesterov"]), first,
+                           _p(grad_scale), _p(found_inf), int(self.zero_grad_in_step), sp)
+            # (a first step skipped on the device leaves the buffer zero and `first` stale: the
+            # next one then runs momentum * 0 + (1 - dampening) d, as flat SGD does)
+        else:
+            if found_inf is not None and bool(found_inf.item() != 0):
+                self.kskip += 1  # (as flat SGD's CPU path; the rule has no step count)
+                if self.zero_grad_in_step:  # a skipped step still clears the gradient
+                    flat.grad.zero_()
+                return
+            c = grad_scale.to(flat.grad.device).reshape(()) if grad_scale is not None else None
+            for si, sl in enumerate(flat.slots):
+                p, gr = self._slot_views(sl, flat.data, flat.grad)
+                _, _, adapted, decayed = self._slot_host[si].tolist()
+                wn = float(torch.linalg.vector_norm(p, dtype=torch.float64)) if sl.numel else 0.0
+                gn = float(torch.linalg.vector_norm(gr, dtype=torch.float64)) if sl.numel else 0.0
+                if c is not None:
+                    gn *= float(c)
+                wd_s = wd if decayed else 0.0
+                q = 1.0
+                if adapted and wn > 0 and gn > 0:
+                    q = g["eta"] * wn / (gn + wd_s * wn + g["eps"])
+                self.trust[si] = q
+                self.norms[si, 0], self.norms[si, 1] = wn, gn
+                qf = self.trust[si]  # fp32, as the kernel reads it
+                qc = qf * c if c is not None else qf
+                qwd = float(qf * torch.tensor(wd_s, dtype=torch.float32))
+                d = gr * qc if (c is not None or q != 1.0) else gr
+                d = d + qwd * p if qwd != 0 else d.clone()
+                if buf is not None:
+                    b, = self._slot_views(sl, buf)
+                    if first:
+                        b.copy_(d)
+                    else:
+                        b.mul_(g["momentum"]).add_(d, alpha=1 - g["dampening"])
+                    d = d + g["momentum"] * b if g["nesterov"] else b
+                p.add_(d, alpha=-g["lr"])
+            self._finish_cpu()
+        if buf is not None:
+            self.state["__flat__"]["initialized"] = 1
+
+
+class LAMB(LayerwiseOptimizer):
+    """AdamW with a layer-wise trust ratio (You et al. 2019), decoupled decay only.  With the clip
+    coefficient c and t = applied steps:  g' = c g,  m = b1 m + (1-b1) g',  v = b2 v + (1-b2) g'^2,
+    u = (m / (1-b1^t)) / (sqrt(v / (1-b2^t)) + eps) + wd_s p,
+    q_s = |p_s| / |u_s| if the slot is adapted and both > 0, else 1;  p -= lr q_s u.
+    1-D slots are excluded by default (q = 1, no decay).
+
+    Three launches per step (``optim_layerwise.hip``): lamb_moments (m, v in place and the per-tile
+    sums of p^2 and u^2), slot_finalize, lamb_apply (u recomputed from m, v, p: no u buffer; this
+    pass zeroes the gradient and counts a skipped step).  No host sync.  The fused
+    update-and-pack path is not used (see ``LayerwiseOptimizer``)."""
+
+    def __init__(self, flat, lr=1e-3, betas=(0.9, 0.999), eps=1e-6, weight_decay=0.0, exclude_1d=True, **kw):
+        super().__init__(flat, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, exclude_1d=exclude_1d),
+                         **kw)
+
+    def _step(self, grad_scale, found_inf):
+        g = self.group
+        flat = self.flat
+        tiles, slot_rows = self._tables()
+        m = self._state_buf("exp_avg")
+        v = self._state_buf("exp_avg_sq")
+        b1, b2 = g["betas"]
+        wd = float(g["weight_decay"])
+        if self._native:
+            nat, sp = _native.native(), _sp()
+            nat.lamb_moments(flat.data.data_ptr(), flat.grad.data_ptr(), m.data_ptr(), v.data_ptr(), tiles.data_ptr(),
+                             self.ntiles, slot_rows.data_ptr(), self.part.data_ptr(), float(b1), float(b2),
+                             float(g["eps"]), wd, self.k + 1, self.kskip.data_ptr(), _p(grad_scale), _p(found_inf), sp)
+            nat.slot_finalize(self.part.data_ptr(), slot_rows.data_ptr(), self.nslots, 1, 0.0, wd, float(g["eps"]), 0,
+                              _p(found_inf), self.trust.data_ptr(), self.norms.data_ptr(), sp)
+            nat.lamb_apply(flat.data.data_ptr(), flat.grad.data_ptr(), m.data_ptr(), v.data_ptr(), _p(flat.shadow),
+                           tiles.data_ptr(), self.ntiles, slot_rows.data_ptr(), self.trust.data_ptr(), float(g["lr"]),
+                           float(b1), float(b2), float(g["eps"]), wd, self.k + 1, self.kskip.data_ptr(),
+                           _p(found_inf), int(self.zero_grad_in_step), sp)
+            return
+        gr_all = self._cpu_common(grad_scale, found_inf)
+        if gr_all is None:
+            return
+        step = self.applied_k + 1
+        bc1, bc2 = 1 - b1 ** step, 1 - b2 ** step
+        for si, sl in enumerate(flat.slots):
+            p, gr, ms, vs = self._slot_views(sl, flat.data, gr_all, m, v)
+            _, _, adapted, decayed = self._slot_host[si].tolist()
+            ms.mul_(b1).add_(gr, alpha=1 - b1)
+            vs.mul_(b2).addcmul_(gr, gr, value=1 - b2)
+            u = (ms / bc1) / ((vs / bc2).sqrt_().add_(g["eps"]))
+            if decayed and wd != 0:
+                u = u + wd * p
+            wn = float(torch.linalg.vector_norm(p, dtype=torch.float64)) if sl.numel else 0.0
+            un = float(torch.linalg.vector_norm(u, dtype=torch.float64)) if sl.numel else 0.0
+            q = wn / un if (adapted and wn > 0 and un > 0) else 1.0
+            self.trust[si] = q
+            self.norms[si, 0], self.norms[si, 1] = wn, un
+            p.add_(u, alpha=-float(torch.tensor(g["lr"], dtype=torch.float32) * self.trust[si]))
         self._finish_cpu()
 
 

@@ -119,6 +119,15 @@ class JsonlLogger:
                 f.write(json.dumps(kw) + "\n")
 
 
+def trust_record(optimizer) -> dict:
+    """The epoch record's trust_min / trust_med / trust_max (last step, adapted slots) of an
+    optimizer that has trust ratios (LARS / LAMB); empty for every other one, whose runs write
+    exactly the records they always wrote."""
+    summary = getattr(optimizer, "trust_summary", None)
+    t = summary() if summary is not None else None
+    return {} if t is None else {"trust_min": t["min"], "trust_med": t["med"], "trust_max": t["max"]}
+
+
 def peak_memory_gb(device=None) -> float:
     if torch.cuda.is_available():
         return torch.cuda.max_memory_allocated(device) / 1024**3

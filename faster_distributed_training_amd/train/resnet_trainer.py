@@ -24,14 +24,15 @@ from ..models import resnet as resnet_models
 from ..ops.mixup import (unit_grad, MetaMixup, cutmix_data, mixup_criterion, mixup_criterion_meta,
                          mixup_cross_entropy, mixup_data)
 from ..ops.resnet_fused import STAGES
-from ..optim.flat_optim import MADGRAD, SGD, Adam, DeviceGradScaler, GradClipper, MirrorMADGRAD
+from ..optim.flat_optim import (LAMB, LARS, MADGRAD, SGD, Adam, DeviceGradScaler, GradClipper, MirrorMADGRAD,
+                                 check_layerwise_config)
 from ..optim.ngd import NGD
 from ..parallel import dist as pdist
 from ..utils.env import default_device, print0, seed_everything
 from ..utils.flat import FlatParams
 from . import checkpoint as ckpt
 from . import resilience
-from .metrics import DeviceMeter, JsonlLogger, PhaseProfiler, draw_graph, peak_memory_gb
+from .metrics import DeviceMeter, JsonlLogger, PhaseProfiler, draw_graph, peak_memory_gb, trust_record
 
 
 @dataclass
@@ -93,6 +94,7 @@ class ResNetConfig:
     cutmix_alpha: float = 1.0          # Beta(alpha, alpha) for the CutMix box area
     cutmix_per_sample: bool = False    # a box per sample (default: one box per batch, as the paper)
     label_smoothing: float = 0.0       # training loss only: the evaluation loss stays unsmoothed
+    trust_coef: float = 1e-3           # LARS eta (--optimizer lars); <= 0 switches the trust ratio off
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
@@ -153,6 +155,7 @@ class ResNetTrainer:
         self.cfg = cfg
         # (before any process group is set up)
         check_eval_config(cfg.eval_stats, cfg.fsdp, cfg.calibrate_batches, cfg.eval_only, cfg.resume)
+        check_layerwise_config(cfg.optimizer, cfg.fsdp)
         self.rank, self.world = 0, 1
         if (cfg.distributed or cfg.fsdp or cfg.force_sharded or cfg.force_ddp
                 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
@@ -316,6 +319,12 @@ class ResNetTrainer:
         elif kind in ("adam", "adamw"):
             wd = 0.0 if cfg.weight_decay is None else cfg.weight_decay
             opt = Adam(self.space, lr=lr, weight_decay=wd, adamw=(kind == "adamw"))
+        elif kind == "lars":  # the SGD recipe with layer-wise trust ratios (large batch / many GPUs)
+            wd = 5e-4 if cfg.weight_decay is None else cfg.weight_decay
+            opt = LARS(self.space, lr=lr, momentum=cfg.momentum, weight_decay=wd, eta=cfg.trust_coef)
+        elif kind == "lamb":
+            wd = 0.01 if cfg.weight_decay is None else cfg.weight_decay
+            opt = LAMB(self.space, lr=lr, weight_decay=wd)
         else:
             raise ValueError(kind)
         sched = cfg.scheduler
@@ -460,6 +469,7 @@ class ResNetTrainer:
                    train_acc=m["acc"], peak_mem_gb=peak_memory_gb(), lr=self.optimizer.group["lr"],
                    skipped_steps=int(self.skipped.item()))
         self.skipped.zero_()
+        rec.update(trust_record(self.optimizer))
         print0(f"epoch {epoch}: {n} steps in {dt:.2f}s ({rec['img_per_s']:.0f} img/s) loss {m['loss']:.4f} "
                f"acc {m['acc']:.2f}%  peak mem {rec['peak_mem_gb']:.2f} GB")
         self.logger.log(**rec)

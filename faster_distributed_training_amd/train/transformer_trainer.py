@@ -25,7 +25,8 @@ import torch.nn as nn
 from ..data.agnews import NUM_CLASSES, TextBatchLoader, download_agnews, get_tokenizer, load_agnews
 from ..models.transformer import Transformer
 from ..ops.mixup import mixup_criterion, unit_grad
-from ..optim.flat_optim import SGD, Adam, DeviceGradScaler, GradClipper, MirrorMADGRAD, MADGRAD
+from ..optim.flat_optim import (LAMB, LARS, SGD, Adam, DeviceGradScaler, GradClipper, MirrorMADGRAD, MADGRAD,
+                                 check_layerwise_config)
 from ..optim.ngd import NGD
 from ..parallel import dist as pdist
 from ..ops import _native
@@ -34,7 +35,7 @@ from ..utils.env import default_device, print0, seed_everything
 from ..utils.flat import FlatParams
 from . import checkpoint as ckpt
 from . import resilience
-from .metrics import DeviceMeter, JsonlLogger, PhaseProfiler, draw_graph, peak_memory_gb
+from .metrics import DeviceMeter, JsonlLogger, PhaseProfiler, draw_graph, peak_memory_gb, trust_record
 
 TR_GRAPHS = os.environ.get("FDT_TR_GRAPHS", "1") != "0"
 # linear / LayerNorm / embedding backward kernels accumulate straight into the flat fp32
@@ -96,12 +97,14 @@ class TransformerConfig:
     save_last: bool = False
     nonfinite_guard: bool = True     # skip (on device) steps whose gradients are not finite
     profile_steps: int = 0
+    trust_coef: float = 1e-3         # LARS eta (--optimizer lars); <= 0 switches the trust ratio off
     extra: dict = field(default_factory=dict)
 
 
 class TransformerTrainer:
     def __init__(self, cfg: TransformerConfig):
         self.cfg = cfg
+        check_layerwise_config(cfg.optimizer, cfg.fsdp or (cfg.distributed and cfg.faithful))
         self.rank, self.world = 0, 1
         if cfg.distributed or cfg.fsdp or int(os.environ.get("WORLD_SIZE", "1")) > 1:
             # (--fsdp always runs the sharded path, over a world-1 group on one GPU)
@@ -266,6 +269,10 @@ class TransformerTrainer:
             opt = SGD(self.space, lr=lr, momentum=0.0, weight_decay=wd or 0.0)
         elif kind in ("adam", "adamw"):
             opt = Adam(self.space, lr=lr, weight_decay=wd or 0.0, adamw=kind == "adamw")
+        elif kind == "lamb":  # the AdamW recipe with layer-wise trust ratios (large batch / many GPUs)
+            opt = LAMB(self.space, lr=lr, weight_decay=0.01 if wd is None else wd)
+        elif kind == "lars":
+            opt = LARS(self.space, lr=lr, momentum=0.9, weight_decay=5e-4 if wd is None else wd, eta=cfg.trust_coef)
         else:
             raise ValueError(kind)
         steps = self.cfg.steps_per_epoch or len(self.train_loader)
@@ -488,6 +495,7 @@ class TransformerTrainer:
                    train_acc=m["acc"], peak_mem_gb=peak_memory_gb(), lr=self.optimizer.group["lr"],
                    skipped_steps=int(self.skipped.item()))
         self.skipped.zero_()
+        rec.update(trust_record(self.optimizer))
         print0(f"epoch {epoch}: {n} steps in {dt:.2f}s ({rec['samples_per_s']:.0f} samples/s) loss {m['loss']:.4f} "
                f"acc {m['acc']:.2f}%  peak mem {rec['peak_mem_gb']:.2f} GB")
         self.logger.log(**rec)

@@ -20,6 +20,11 @@ and the training-recipe switches:
   --cutmix_per_sample            a box per sample (default: one box per batch)
   --label_smoothing E            smoothing of the training loss, 0 <= E < 1 (the evaluation loss stays unsmoothed)
 
+and the large-batch optimizers (layer-wise trust ratios, ``optim/flat_optim.py`` LARS / LAMB):
+
+  --optimizer {lars,lamb}        besides every value ``resnet50_test.py`` takes, which are passed on to it
+  --trust_coef ETA               LARS trust coefficient (default 1e-3; <= 0: no trust ratio, plain SGD)
+
 Without the new switches it behaves exactly like ``resnet50_test.py``.
 
 Examples:
@@ -28,6 +33,7 @@ Examples:
     python resnet_infer.py --eval_stats running --calibrate_batches 8 --resume --eval_only
     python resnet_infer.py --dataset cifar100 --synthetic --bs 256 --epoch 1
     python resnet_infer.py --dataset cifar100 --cutmix_prob 0.5 --label_smoothing 0.1
+    python resnet_infer.py --synthetic --bs 1024 --optimizer lars --lr 0.4
 """
 from __future__ import annotations
 
@@ -60,12 +66,21 @@ def parse(argv=None):
     p.add_argument("--cutmix_per_sample", action="store_true", help="a CutMix box per sample (default: one per batch)")
     p.add_argument("--label_smoothing", default=0.0, type=float,
                    help="label smoothing of the training loss, in [0, 1); the evaluation loss stays unsmoothed")
+    p.add_argument("--optimizer", default=None,
+                   help="lars / lamb: layer-wise trust ratios (SGD / AdamW form); any other value is resnet50_test.py's")
+    p.add_argument("--trust_coef", default=1e-3, type=float,
+                   help="--optimizer lars: trust coefficient eta (<= 0: no trust ratio, plain SGD)")
     argv = list(sys.argv[1:] if argv is None else argv)
     if "-h" in argv or "--help" in argv:
         p.print_help()
         print()
     a, rest = p.parse_known_args(argv)
+    from faster_distributed_training_amd.optim.flat_optim import LAYERWISE, check_layerwise_config
+    if a.optimizer is not None and a.optimizer not in LAYERWISE:
+        rest += ["--optimizer", a.optimizer]  # (one of its own: it checks the choice)
+        a.optimizer = None
     base = resnet50_test.parse(rest)
+    check_layerwise_config(a.optimizer or base.optimizer, base.fsdp)  # (a ValueError, with the reason)
     from faster_distributed_training_amd.train.resnet_trainer import check_eval_config, check_mix_config
     try:
         check_eval_config(a.eval_stats, base.fsdp, a.calibrate_batches, a.eval_only, base.resume)
@@ -81,7 +96,8 @@ def config_from_args(a, base):
                                calibrate_batches=a.calibrate_batches, eval_only=a.eval_only,
                                dataset=a.dataset, num_classes=None, cutmix_prob=a.cutmix_prob,
                                cutmix_alpha=a.cutmix_alpha, cutmix_per_sample=a.cutmix_per_sample,
-                               label_smoothing=a.label_smoothing)
+                               label_smoothing=a.label_smoothing, trust_coef=a.trust_coef,
+                               **({"optimizer": a.optimizer} if a.optimizer else {}))
 
 
 def main(argv=None):

@@ -6,6 +6,7 @@
 #   NGPU=8 bash run_distributed.sh resnet    # one of them
 #   MAX_RESTARTS=3 bash run_distributed.sh resnet --auto_resume
 #   NGPU=8 bash run_distributed.sh resnet --eval_stats running    # track statistics, evaluate frozen
+#   NGPU=8 bash run_distributed.sh transformer --optimizer lamb --lr 1e-3   # large batch: layer-wise trust ratios
 #       elastic restarts: a failed/killed rank restarts the whole job, which resumes from the
 #       full-state checkpoint of the last completed epoch (checkpoint/*_last.pth)
 set -euo pipefail
@@ -20,5 +21,6 @@ if [[ "$WHAT" == all || "$WHAT" == resnet ]]; then
   $RUN ./resnet_infer.py --workers 4 --bs $((1024 / NGPU)) --distributed --meta_learning --ngd --lr 0.01 "${@:2}"
 fi
 if [[ "$WHAT" == all || "$WHAT" == transformer ]]; then
-  $RUN ./transformer_test.py --workers 4 --batch_size $((256 / NGPU)) --distributed --ngd "${@:2}"
+  # (transformer_train.py: transformer_test.py's CLI plus --optimizer lars|lamb / --trust_coef)
+  $RUN ./transformer_train.py --workers 4 --batch_size $((256 / NGPU)) --distributed --ngd "${@:2}"
 fi
