@@ -79,6 +79,13 @@ void lamb_moments(uint64_t p, uint64_t g, uint64_t m, uint64_t v, uint64_t tiles
 void lamb_apply(uint64_t p, uint64_t g, uint64_t m, uint64_t v, uint64_t shadow, uint64_t tiles, int ntiles,
                 uint64_t slots, uint64_t trust, float lr, float b1, float b2, float eps, float wd, long step,
                 uint64_t kskip, uint64_t found_inf, int zero_grad, uint64_t stream);
+// weight EMA over the flat buffer (ema.hip): e <- fmaf(d, e - p, p), d = decay or (warmup)
+// min(decay, (1 + t) / (10 + t)) with t = k - *kskip; found_inf set: e untouched, *kskip += 1.
+// ema_swap exchanges p and e in place and writes shadow = bf16(new p) where shadow != 0.
+std::vector<int> ema_launch_config();  // {threads per workgroup, vectors per thread and trip, grid cap}
+void ema_update(uint64_t p, uint64_t e, long n, float decay, int warmup, long k, uint64_t kskip, uint64_t found_inf,
+                uint64_t stream);
+void ema_swap(uint64_t p, uint64_t e, uint64_t shadow, long n, uint64_t stream);
 // fused optimizer step + conv weight repack (optim_pack.hip): tab = int64 [ntab, 8] entries
 // (flat offset, wf, wd, Cout, Cin, Cxp, ntaps, first block), rr = int64 [nrr, 3] rest ranges
 void madgrad_pack_step(uint64_t p, uint64_t g, uint64_t gss, uint64_t s, uint64_t x0, uint64_t shadow, long n,

@@ -8,7 +8,9 @@ DDP checkpoints carry a ``module.`` prefix — we *write* that prefix when
 loading (the reference's distributed resume fails on the prefix mismatch).
 
 Extras live under additional keys the reference loader ignores: ``optimizer``
-(incl. NGD state), ``scheduler``, ``scaler``, ``rng``; plus a rolling "last" file.
+(incl. NGD state), ``scheduler``, ``scaler``, ``rng``, ``ema`` (the averaged weights of a run
+with ``--ema_decay``: ``net`` in this schema, ``updates``, ``decay``, ``fused_stats``); plus a
+rolling "last" file.
 Writes are rank-0 only, atomic (tmp + rename), followed by a barrier (Q16).
 Loads use ``weights_only=True``.
 """

@@ -4,8 +4,8 @@ GradScaler's inf skip, resnet50_test.py:541-548, 664-690).
 
 * ``save_last`` / ``restore_last``: a rolling full-state checkpoint (``*_last.pth``) written
   at the end of every epoch by rank 0 -- model (reference schema, so the reference loader
-  reads it), optimizer (flat state incl. NGD preconditioners), scheduler, loss scaler,
-  best accuracy, global step, and every RNG stream (python, numpy, torch CPU / device, the
+  reads it), optimizer (flat state incl. NGD preconditioners), scheduler, loss scaler, the
+  weight EMA where one is kept (``ema_state``: ``optim/ema.py``), best accuracy, global step, and every RNG stream (python, numpy, torch CPU / device, the
   device data loader's counter RNG) so a resumed run continues the same random sequence.
   Loads use ``weights_only=True``; numpy/python RNG states are stored as tensors/ints.
 * per-rank state lives in ``*_last.rank{r}.pth`` next to the main file (every rank writes
@@ -153,7 +153,10 @@ def save_last(trainer, epoch: int):
     meta = getattr(trainer, "meta", None)
     if meta is not None:
         extra["meta"] = {k: v.detach().cpu() for k, v in meta.state_dict().items()}
-    acc = trainer.testing_acc[-1] if getattr(trainer, "testing_acc", None) else 0.0
+    ema = getattr(trainer, "ema", None)
+    if ema is not None:
+        extra["ema_state"] = ema.state_dict()  # (the average itself, its counters and slot table)
+    acc =trainer.testing_acc[-1] if getattr(trainer, "testing_acc", None) else 0.0
     ckpt.save_checkpoint(trainer.last_path, trainer.model, acc, epoch, module_prefix=False, extra=extra)
     _drop_stale_rank_files(trainer.last_path, rank, epoch)  # (after the main file's commit + barrier)
 
@@ -196,6 +199,10 @@ def restore_last(trainer) -> bool:
         trainer.scaler.load_state_dict(ck["scaler"])
     if "meta" in ck and getattr(trainer, "meta", None) is not None:
         trainer.meta.load_state_dict(ck["meta"])
+    if getattr(trainer, "ema", None) is not None:
+        if "ema_state" not in ck:
+            raise RuntimeError(f"{path} carries no EMA state: it was written by a run without --ema_decay")
+        trainer.ema.load_state_dict(ck["ema_state"])
     trainer.global_step = int(ck.get("global_step", 0))
     trainer.best_acc = max(float(trainer.best_acc), float(ck.get("best_acc", 0.0)))
     trainer.start_epoch = int(ck["epoch"]) + 1

@@ -26,6 +26,7 @@ from ..ops.mixup import (unit_grad, MetaMixup, cutmix_data, mixup_criterion, mix
 from ..ops.resnet_fused import STAGES
 from ..optim.flat_optim import (LAMB, LARS, MADGRAD, SGD, Adam, DeviceGradScaler, GradClipper, MirrorMADGRAD,
                                  check_layerwise_config)
+from ..optim.ema import FlatEMA, check_ema_config
 from ..optim.ngd import NGD
 from ..parallel import dist as pdist
 from ..utils.env import default_device, print0, seed_everything
@@ -95,6 +96,11 @@ class ResNetConfig:
     cutmix_per_sample: bool = False    # a box per sample (default: one box per batch, as the paper)
     label_smoothing: float = 0.0       # training loss only: the evaluation loss stays unsmoothed
     trust_coef: float = 1e-3           # LARS eta (--optimizer lars); <= 0 switches the trust ratio off
+    ema_decay: float = 0.0             # > 0: average the weights after every step (optim/ema.py), evaluate the average
+    ema_warmup: bool = True            # d = min(ema_decay, (1 + t) / (10 + t)) over the applied updates t
+    warmup_epochs: float = 0.0         # > 0: linear per-step LR warm-up over round(warmup_epochs * steps per epoch) steps
+    warmup_start_factor: float = 0.1   # the first step's share of the scheduled rate
+    eval_ema: bool = False             # with resume + eval_only: score the checkpoint's averaged weights ("ema" entry)
     extra: dict = field(default_factory=dict)
 
     def __post_init__(self):
@@ -106,6 +112,43 @@ class ResNetConfig:
         elif self.dataset == "cifar100" and self.num_classes != n:
             raise ValueError(f"dataset 'cifar100' has {n} classes: num_classes={self.num_classes} conflicts")
         check_mix_config(self.cutmix_prob, self.label_smoothing, self.meta_learning)
+        check_warmup_config(self.warmup_epochs, self.warmup_start_factor)
+
+
+def check_warmup_config(warmup_epochs: float = 0.0, warmup_start_factor: float = 0.1):
+    """Refuses an LR warm-up that is no ramp (the configs' __post_init__ and the CLIs call it)."""
+    if warmup_epochs < 0:
+        raise ValueError(f"--warmup_epochs must be >= 0, not {warmup_epochs}")
+    if not 0.0 <= warmup_start_factor <= 1.0:
+        raise ValueError(f"--warmup_start_factor must be in [0, 1], not {warmup_start_factor}")
+
+
+def warmup_factor(step: int, warmup_steps: int, start: float):
+    """Share of the scheduled rate that global step ``step`` takes: linear from ``start`` at step 0
+    to 1 at ``warmup_steps``; None from there on (the rate is not touched)."""
+    if step >= warmup_steps:
+        return None
+    return start + (1.0 - start) * step / warmup_steps
+
+
+class scaled_lr:
+    """``group["lr"]`` times ``f`` for the duration of one ``optimizer.step``: the value is put back
+    afterwards, so recursive torch schedulers (CosineAnnealingLR) never see the scaled rate.  NGD
+    fills its device ``lr_dev`` from ``group["lr"]`` at every step, eager or replayed."""
+
+    def __init__(self, optimizer, f):
+        self.groups, self.f = optimizer.param_groups, f
+
+    def __enter__(self):
+        self.saved = [g["lr"] for g in self.groups]
+        for g in self.groups:
+            g["lr"] = g["lr"] * self.f
+        return self
+
+    def __exit__(self, *exc):
+        for g, lr in zip(self.groups, self.saved):
+            g["lr"] = lr
+        return False
 
 
 def check_eval_config(eval_stats: str, fsdp: bool = False, calibrate_batches: int = 0, eval_only: bool = False,
@@ -156,6 +199,13 @@ class ResNetTrainer:
         # (before any process group is set up)
         check_eval_config(cfg.eval_stats, cfg.fsdp, cfg.calibrate_batches, cfg.eval_only, cfg.resume)
         check_layerwise_config(cfg.optimizer, cfg.fsdp)
+        # (sharded NGD is known here when it is forced or the launcher started several ranks; the
+        # ZeRO-2 branch below checks again once the world size is)
+        check_ema_config(cfg.ema_decay, cfg.fsdp, sharded=bool(
+            not cfg.fsdp and cfg.shard_ngd and (cfg.optimizer == "ngd" or (cfg.optimizer == "auto" and cfg.ngd))
+            and (cfg.force_sharded or int(os.environ.get("WORLD_SIZE", "1")) > 1)))
+        if cfg.eval_ema and not (cfg.resume and cfg.eval_only):
+            raise ValueError("--eval_ema scores a checkpoint's averaged weights: pass --resume --eval_only")
         self.rank, self.world = 0, 1
         if (cfg.distributed or cfg.fsdp or cfg.force_sharded or cfg.force_ddp
                 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
@@ -173,6 +223,11 @@ class ResNetTrainer:
         self.best_acc, self.start_epoch = ckpt.load_best_performance(self.ckpt_path, cfg.num_classes, cfg.resume)
         if cfg.resume:
             ck = ckpt.load_checkpoint(self.ckpt_path)
+            if cfg.eval_ema:
+                if "ema" not in ck:
+                    raise RuntimeError(f"{self.ckpt_path} carries no averaged weights (no 'ema' entry): it was "
+                                       f"not trained with --ema_decay")
+                ck = dict(ck["ema"])  # ("net": the averaged weights, "fused_stats": what they were scored with)
             ckpt.load_model_state(self.model, ck["net"])
             self._load_fused_stats(ck, self.ckpt_path)
         self.meta = None
@@ -209,6 +264,7 @@ class ResNetTrainer:
             # ZeRO-2 for NGD: each rank preconditions + updates only the parameters it owns
             # (parallel/zero.py) instead of every rank repeating the whole NGD step
             from ..parallel.zero import ShardedOptimizerDP
+            check_ema_config(cfg.ema_decay, sharded=True)
             self.flat = FlatParams(params_owner, device=self.device, partition=self.world, balance="ngd")
             cdt = {"fp32": None, "bf16": torch.bfloat16}[cfg.comm_dtype]
             self.zero = ShardedOptimizerDP(self.flat, self.model, bucket_mb=cfg.bucket_mb,
@@ -229,6 +285,10 @@ class ResNetTrainer:
         self.clipper = GradClipper(self.space, sharded=self.sharder is not None)
         self.scaler = DeviceGradScaler(self.device, enabled=(cfg.precision == "fp16"))
         self._build_data()
+        # (both None / 0 by default: such a run builds no FlatEMA and never touches group["lr"])
+        self.ema = FlatEMA(self.flat, cfg.ema_decay, cfg.ema_warmup) if cfg.ema_decay > 0 else None
+        self.warmup_steps = int(round(cfg.warmup_epochs * (cfg.steps_per_epoch or len(self.train_loader))))
+        self.lr_last_step = None
         self.meter = DeviceMeter(self.device)
         self.logger = JsonlLogger(cfg.log_path)
         if cfg.cutmix_prob > 0 or cfg.label_smoothing > 0:
@@ -428,7 +488,16 @@ class ResNetTrainer:
         if fp16 or (check and self.sharder is not None):
             # fp16 / sharded gradients: every rank must take the same decision
             self.scaler.sync_found_inf(self.clipper.found_inf)
-        self.optimizer.step(grad_scale=self.clipper.coef, found_inf=found)
+        f = warmup_factor(self.global_step, self.warmup_steps, cfg.warmup_start_factor) if self.warmup_steps else None
+        if f is None:
+            self.optimizer.step(grad_scale=self.clipper.coef, found_inf=found)
+        else:
+            with scaled_lr(self.optimizer, f):
+                self.optimizer.step(grad_scale=self.clipper.coef, found_inf=found)
+        if self.warmup_steps:
+            self.lr_last_step = self.optimizer.group["lr"] * (1.0 if f is None else f)
+        if self.ema is not None:
+            self.ema.update(found_inf=found)  # (a step skipped on the device skips the average too)
         if fp16:
             self.scaler.update(found)
         if guard:
@@ -470,6 +539,10 @@ class ResNetTrainer:
                    skipped_steps=int(self.skipped.item()))
         self.skipped.zero_()
         rec.update(trust_record(self.optimizer))
+        if self.warmup_steps:
+            rec["lr_last_step"] = self.lr_last_step
+        if self.ema is not None:
+            rec["ema_decay_eff"] = self.ema.decay_eff()  # (host view of k - kskip: the epoch's sync is above)
         print0(f"epoch {epoch}: {n} steps in {dt:.2f}s ({rec['img_per_s']:.0f} img/s) loss {m['loss']:.4f} "
                f"acc {m['acc']:.2f}%  peak mem {rec['peak_mem_gb']:.2f} GB")
         self.logger.log(**rec)
@@ -479,6 +552,24 @@ class ResNetTrainer:
 
     @torch.no_grad()
     def test(self, epoch, save=True):
+        if self.ema is None:
+            return self._test(epoch, save)
+        # evaluate the averaged weights and leave the training state as it was: weights and bf16
+        # shadow are swapped back bitwise (the packed conv layouts go stale with each swap), and
+        # running statistics re-estimated for the averaged weights do not leak into training
+        calibrated = self.cfg.calibrate_batches > 0
+        self._train_stats = self.fused_stats() if calibrated else None  # (what the checkpoint keeps next to "net")
+        saved = [(b, b.detach().clone()) for b in self.model.buffers()] if calibrated else []
+        try:
+            with self.ema.applied():
+                return self._test(epoch, save)
+        finally:
+            for b, was in saved:  # FusedConvBN (and BatchNorm2d) running statistics, in place
+                b.copy_(was)
+            self._train_stats = None
+
+    @torch.no_grad()
+    def _test(self, epoch, save=True):
         if self.cfg.calibrate_batches > 0:
             self.calibrate()
         # every rank evaluates with rank 0's running statistics (reference DDP broadcasts
@@ -514,13 +605,36 @@ class ResNetTrainer:
             stats = self.fused_stats()
             if stats is not None:
                 extra = dict(extra or {}, fused_stats=stats)
-            ckpt.save_checkpoint(self.ckpt_path, self.model, acc, epoch, module_prefix=prefix, extra=extra)
+            if self.ema is not None:
+                extra = self._ema_checkpoint(extra, stats, prefix)
+                self.ema.swap()  # "net" stays the trained weights: --resume continues the same trajectory
+                try:
+                    ckpt.save_checkpoint(self.ckpt_path, self.model, acc, epoch, module_prefix=prefix, extra=extra)
+                finally:
+                    self.ema.swap()
+            else:
+                ckpt.save_checkpoint(self.ckpt_path, self.model, acc, epoch, module_prefix=prefix, extra=extra)
             self.best_acc = acc
         if top5:
             self.logger.log(epoch=epoch, test_acc=acc, test_top5=acc5)
         else:
             self.logger.log(epoch=epoch, test_acc=acc)
         return acc
+
+    def _ema_checkpoint(self, extra, stats, prefix):
+        """The best checkpoint's "ema" entry (called with the averaged weights swapped in): the
+        averaged weights in the reference schema, the update count, the decay and -- under
+        --eval_stats running -- the statistics the score was taken with."""
+        entry = {"net": ckpt.model_state(self.model, prefix), "updates": int(self.ema.applied_k),
+                 "decay": float(self.ema.decay)}
+        if stats is not None:
+            entry["fused_stats"] = stats
+        extra = dict(extra or {}, ema=entry)
+        if getattr(self, "_train_stats", None) is not None:
+            # (statistics calibrated under the averaged weights belong to the "ema" entry alone:
+            # next to the trained "net" go the ones training left, restored after the evaluation)
+            extra["fused_stats"] = self._train_stats
+        return extra
 
     def evaluate_only(self):
         """--eval_only: score the loaded checkpoint once (nothing is trained or saved)."""

@@ -27,6 +27,7 @@ from ..models.transformer import Transformer
 from ..ops.mixup import mixup_criterion, unit_grad
 from ..optim.flat_optim import (LAMB, LARS, SGD, Adam, DeviceGradScaler, GradClipper, MirrorMADGRAD, MADGRAD,
                                  check_layerwise_config)
+from ..optim.ema import FlatEMA, check_ema_config
 from ..optim.ngd import NGD
 from ..parallel import dist as pdist
 from ..ops import _native
@@ -35,6 +36,7 @@ from ..utils.env import default_device, print0, seed_everything
 from ..utils.flat import FlatParams
 from . import checkpoint as ckpt
 from . import resilience
+from .resnet_trainer import check_warmup_config, scaled_lr, warmup_factor
 from .metrics import DeviceMeter, JsonlLogger, PhaseProfiler, draw_graph, peak_memory_gb, trust_record
 
 TR_GRAPHS = os.environ.get("FDT_TR_GRAPHS", "1") != "0"
@@ -98,13 +100,23 @@ class TransformerConfig:
     nonfinite_guard: bool = True     # skip (on device) steps whose gradients are not finite
     profile_steps: int = 0
     trust_coef: float = 1e-3         # LARS eta (--optimizer lars); <= 0 switches the trust ratio off
+    ema_decay: float = 0.0           # > 0: average the weights after every step (optim/ema.py), evaluate the average
+    ema_warmup: bool = True          # d = min(ema_decay, (1 + t) / (10 + t)) over the applied updates t
+    warmup_epochs: float = 0.0       # > 0: linear per-step LR warm-up on top of the scheduler's rate
+    warmup_start_factor: float = 0.1
     extra: dict = field(default_factory=dict)
+
+    def __post_init__(self):
+        check_warmup_config(self.warmup_epochs, self.warmup_start_factor)
 
 
 class TransformerTrainer:
     def __init__(self, cfg: TransformerConfig):
         self.cfg = cfg
         check_layerwise_config(cfg.optimizer, cfg.fsdp or (cfg.distributed and cfg.faithful))
+        check_ema_config(cfg.ema_decay, cfg.fsdp or (cfg.distributed and cfg.faithful), sharded=bool(
+            not cfg.fsdp and cfg.shard_ngd and (cfg.optimizer == "ngd" or (cfg.optimizer == "auto" and cfg.ngd))
+            and int(os.environ.get("WORLD_SIZE", "1")) > 1))  # (checked again where ZeRO-2 is set up)
         self.rank, self.world = 0, 1
         if cfg.distributed or cfg.fsdp or int(os.environ.get("WORLD_SIZE", "1")) > 1:
             # (--fsdp always runs the sharded path, over a world-1 group on one GPU)
@@ -161,6 +173,7 @@ class TransformerTrainer:
                 from ..ops.linear import enable_shadow_weights
                 enable_shadow_weights(self.flat)
             if part:
+                check_ema_config(cfg.ema_decay, sharded=True)
                 # ZeRO-2 for NGD: every rank preconditions only the parameters it owns
                 from ..parallel.zero import ShardedOptimizerDP
                 self.zero = ShardedOptimizerDP(self.flat, self.model, bucket_mb=cfg.bucket_mb)
@@ -180,6 +193,10 @@ class TransformerTrainer:
         self.optimizer, self.scheduler = self._build_optimizer()
         self.clipper = GradClipper(self.space, sharded=self.sharder is not None)
         self.scaler = DeviceGradScaler(self.device, enabled=(cfg.precision == "fp16"))
+        # (both None / 0 by default: such a run builds no FlatEMA and never touches group["lr"])
+        self.ema = FlatEMA(self.flat, cfg.ema_decay, cfg.ema_warmup) if cfg.ema_decay > 0 else None
+        self.warmup_steps = int(round(cfg.warmup_epochs * (cfg.steps_per_epoch or len(self.train_loader))))
+        self.lr_last_step = None
         self.meter = DeviceMeter(self.device)
         self.logger = JsonlLogger(cfg.log_path)
         self.pos_index = torch.arange(cfg.maxlen, device=self.device)  # transformer_test.py:228
@@ -456,7 +473,16 @@ class TransformerTrainer:
         found = self.clipper.found_inf if check else None
         if fp16 or (check and self.sharder is not None):
             self.scaler.sync_found_inf(self.clipper.found_inf)
-        self.optimizer.step(grad_scale=self.clipper.coef, found_inf=found)
+        f = warmup_factor(self.global_step, self.warmup_steps, cfg.warmup_start_factor) if self.warmup_steps else None
+        if f is None:
+            self.optimizer.step(grad_scale=self.clipper.coef, found_inf=found)
+        else:
+            with scaled_lr(self.optimizer, f):
+                self.optimizer.step(grad_scale=self.clipper.coef, found_inf=found)
+        if self.warmup_steps:
+            self.lr_last_step = self.optimizer.group["lr"] * (1.0 if f is None else f)
+        if self.ema is not None:
+            self.ema.update(found_inf=found)  # (a step skipped on the device skips the average too)
         if fp16:
             self.scaler.update(found)
         if guard:
@@ -496,6 +522,10 @@ class TransformerTrainer:
                    skipped_steps=int(self.skipped.item()))
         self.skipped.zero_()
         rec.update(trust_record(self.optimizer))
+        if self.warmup_steps:
+            rec["lr_last_step"] = self.lr_last_step
+        if self.ema is not None:
+            rec["ema_decay_eff"] = self.ema.decay_eff()  # (host view of k - kskip: the epoch's sync is above)
         print0(f"epoch {epoch}: {n} steps in {dt:.2f}s ({rec['samples_per_s']:.0f} samples/s) loss {m['loss']:.4f} "
                f"acc {m['acc']:.2f}%  peak mem {rec['peak_mem_gb']:.2f} GB")
         self.logger.log(**rec)
@@ -506,7 +536,15 @@ class TransformerTrainer:
     @torch.no_grad()
     def test(self, epoch):
         """Reference ``test`` (``transformer_test.py:300-347``) with Q8 fixed: no mixup in
-        eval and the logits are taken from the returned tuple."""
+        eval and the logits are taken from the returned tuple.  With an EMA the averaged weights
+        are scored: swapped in (weights and bf16 shadow) for the evaluation, bitwise restored after."""
+        if self.ema is None:
+            return self._test(epoch)
+        with self.ema.applied():
+            return self._test(epoch)
+
+    @torch.no_grad()
+    def _test(self, epoch):
         self.model.eval()
         correct = torch.zeros((), device=self.device)
         total = torch.zeros((), device=self.device)
@@ -522,7 +560,19 @@ class TransformerTrainer:
         self.testing_acc.append(acc)
         print0(f"test epoch {epoch}: acc {acc:.2f}%")
         if acc > self.best_acc:
-            ckpt.save_checkpoint(self.ckpt_path, self.model, acc, epoch, module_prefix=self.cfg.distributed)
+            if self.ema is not None:
+                # "net" stays the trained weights (--resume continues the same trajectory); the
+                # averaged ones, which were scored, go into the "ema" entry
+                entry = {"net": ckpt.model_state(self.model, self.cfg.distributed),
+                         "updates": int(self.ema.applied_k), "decay": float(self.ema.decay)}
+                self.ema.swap()
+                try:
+                    ckpt.save_checkpoint(self.ckpt_path, self.model, acc, epoch, module_prefix=self.cfg.distributed,
+                                         extra={"ema": entry})
+                finally:
+                    self.ema.swap()
+            else:
+                ckpt.save_checkpoint(self.ckpt_path, self.model, acc, epoch, module_prefix=self.cfg.distributed)
             self.best_acc = acc
         self.logger.log(epoch=epoch, test_acc=acc)
         return acc

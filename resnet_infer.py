@@ -25,6 +25,14 @@ and the large-batch optimizers (layer-wise trust ratios, ``optim/flat_optim.py``
   --optimizer {lars,lamb}        besides every value ``resnet50_test.py`` takes, which are passed on to it
   --trust_coef ETA               LARS trust coefficient (default 1e-3; <= 0: no trust ratio, plain SGD)
 
+and their companions, a weight EMA (``optim/ema.py``) and a per-step LR warm-up:
+
+  --ema_decay D                  > 0: average the weights after every step, evaluate and checkpoint the average
+  --no_ema_warmup                use D from the first update (default: min(D, (1 + t) / (10 + t)))
+  --warmup_epochs E              linear per-step LR warm-up over E epochs (fractions allowed)
+  --warmup_start_factor F        the first step's share of the scheduled rate (default 0.1)
+  --eval_ema                     with --resume --eval_only: score the checkpoint's averaged weights
+
 Without the new switches it behaves exactly like ``resnet50_test.py``.
 
 Examples:
@@ -34,6 +42,8 @@ Examples:
     python resnet_infer.py --dataset cifar100 --synthetic --bs 256 --epoch 1
     python resnet_infer.py --dataset cifar100 --cutmix_prob 0.5 --label_smoothing 0.1
     python resnet_infer.py --synthetic --bs 1024 --optimizer lars --lr 0.4
+    python resnet_infer.py --bs 1024 --optimizer lars --lr 0.4 --warmup_epochs 5 --ema_decay 0.999
+    python resnet_infer.py --resume --eval_only --eval_ema            # score the averaged weights of a checkpoint
 """
 from __future__ import annotations
 
@@ -70,6 +80,17 @@ def parse(argv=None):
                    help="lars / lamb: layer-wise trust ratios (SGD / AdamW form); any other value is resnet50_test.py's")
     p.add_argument("--trust_coef", default=1e-3, type=float,
                    help="--optimizer lars: trust coefficient eta (<= 0: no trust ratio, plain SGD)")
+    p.add_argument("--ema_decay", default=0.0, type=float,
+                   help="> 0: keep an exponential moving average of the weights (one fused launch per step) and "
+                        "evaluate it; the best checkpoint gains an 'ema' entry")
+    p.add_argument("--no_ema_warmup", action="store_true",
+                   help="use --ema_decay from the first update (default: min(decay, (1 + t) / (10 + t)))")
+    p.add_argument("--warmup_epochs", default=0.0, type=float,
+                   help="linear per-step LR warm-up over this many epochs (fractions allowed), on top of the scheduler")
+    p.add_argument("--warmup_start_factor", default=0.1, type=float,
+                   help="share of the scheduled rate that the first step takes under --warmup_epochs")
+    p.add_argument("--eval_ema", action="store_true",
+                   help="with --resume --eval_only: load the checkpoint's averaged weights ('ema' entry) instead of 'net'")
     argv = list(sys.argv[1:] if argv is None else argv)
     if "-h" in argv or "--help" in argv:
         p.print_help()
@@ -81,8 +102,14 @@ def parse(argv=None):
         a.optimizer = None
     base = resnet50_test.parse(rest)
     check_layerwise_config(a.optimizer or base.optimizer, base.fsdp)  # (a ValueError, with the reason)
-    from faster_distributed_training_amd.train.resnet_trainer import check_eval_config, check_mix_config
+    from faster_distributed_training_amd.optim.ema import check_ema_config
+    from faster_distributed_training_amd.train.resnet_trainer import (check_eval_config, check_mix_config,
+                                                                      check_warmup_config)
     try:
+        check_ema_config(a.ema_decay, base.fsdp)  # (sharded NGD: the trainer refuses, once the world is known)
+        check_warmup_config(a.warmup_epochs, a.warmup_start_factor)
+        if a.eval_ema and not (a.eval_only and base.resume):
+            raise ValueError("--eval_ema scores a checkpoint's averaged weights: pass --resume --eval_only")
         check_eval_config(a.eval_stats, base.fsdp, a.calibrate_batches, a.eval_only, base.resume)
         check_mix_config(a.cutmix_prob, a.label_smoothing, base.meta_learning)
     except ValueError as e:
@@ -97,6 +124,9 @@ def config_from_args(a, base):
                                dataset=a.dataset, num_classes=None, cutmix_prob=a.cutmix_prob,
                                cutmix_alpha=a.cutmix_alpha, cutmix_per_sample=a.cutmix_per_sample,
                                label_smoothing=a.label_smoothing, trust_coef=a.trust_coef,
+                               ema_decay=a.ema_decay, ema_warmup=not a.no_ema_warmup,
+                               warmup_epochs=a.warmup_epochs, warmup_start_factor=a.warmup_start_factor,
+                               eval_ema=a.eval_ema,
                                **({"optimizer": a.optimizer} if a.optimizer else {}))
 
 
