@@ -161,6 +161,13 @@ inline int& conv_write_through_flag() {
   return f;
 }
 inline bool conv_write_through() { return conv_write_through_flag() != 0; }
+// join-backward conv epilogues: operand loads requested a pass ahead (conv_igemm_impl.h
+// conv_epilogue PF); off = the load-per-sweep instantiations
+inline int& conv_epi_prefetch_flag() {
+  static int f = 1;
+  return f;
+}
+inline bool conv_epi_prefetch() { return conv_epi_prefetch_flag() != 0; }
 // cost-probe switches of the conv kernels (never set in training: scripts/conv_probe2.py)
 inline int& conv_debug_flags_ref() {
   static int f = 0;

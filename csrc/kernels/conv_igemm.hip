@@ -206,6 +206,7 @@ void ffn_gemm(uint64_t x, uint64_t w, uint64_t out, long M, int K, int N, int ep
 int conv_num_row_blocks(long M, int BM) { return (int)((M + BM - 1) / BM); }
 
 void set_conv_write_through(bool on) { conv_write_through_flag() = on ? 1 : 0; }
+void set_conv_epi_prefetch(bool on) { conv_epi_prefetch_flag() = on ? 1 : 0; }
 void set_conv_debug_flags(int f) { conv_debug_flags_ref() = f; }
 
 // split-K workspace sizes for a launch: (slab floats, ticket ints)

@@ -285,7 +285,17 @@ struct PixLinear {
   int wstride;
   __device__ __forceinline__ int operator()(int wm, int j, int n) const { return wm * wstride + j * 32 + n; }
 };
-template <int BM, int BN, int EPI, int ACT, int NT, int WM, int WN, class PixF = PixLinear>
+// PF: operand prefetch depth of the ReLU-mask join backward (0: none).  That epilogue's reads
+// (the incoming gradient in `out`, ex, jyb, the mask byte) do not depend on the accumulators, and
+// at short K the kernel is a streaming pass over them: loaded sweep by sweep, each sweep is one
+// serialized memory round trip with 33-49 B per thread in flight.  With PF > 0 the loads of PF
+// sweeps at a time are issued together as raw 16-B registers -- the first group of a pass above
+// that pass's staging stores and barrier -- and unpacked where the sweep used to load them; the
+// arithmetic, its order and the stores are the same.  A hoisted load is unconditional, so a row
+// past M (or a missing jyb) selects the kOOB offset instead of branching: the range check of a
+// buffer descriptor of the tensor's real size answers it with zeros and no memory access.  `out` is read and written in place by the same
+// thread, and every load of a pass is issued before that pass's first store.
+template <int BM, int BN, int EPI, int ACT, int NT, int WM, int WN, class PixF = PixLinear, int PF = 0>
 __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[BN / WN / 32][BM / WM / 32], long m0,
                                               int n0, int bm, int tid, float* stg, float* red, bool ew,
                                               float inv_alpha, PixF pix = PixLinear{BM / WM}) {
@@ -296,6 +306,8 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
   constexpr int RPS = NT / CG;       // rows per sweep
   constexpr int NSW = WM * 32 / RPS;  // sweeps per (WM x 32)-row pass
   static_assert(NSW >= 1 && NSW * RPS == WM * 32, "epilogue sweep geometry");
+  static_assert(PF == 0 || (EPI == kEpiJoinBwd && ACT == kActRelu && NSW % PF == 0),
+                "operand prefetch: the ReLU-mask join backward, whole groups of sweeps");
   constexpr int NW = NT / 64;
   const int lane = tid & 63, wid = tid >> 6, wn = wid % WN, wm = wid / WN;
   constexpr bool STATS = EPI == kEpiStats || EPI == kEpiActBwd || EPI == kEpiJoinBwd;
@@ -305,6 +317,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
   const int cg = tid % CG, rs = tid / CG;
   const int c = n0 + cg * 8;  // this thread's 8 output channels
   const bool dense = a.OS == 1 && a.oy == 0 && a.ox == 0 && a.Hout == a.Ho && a.Wout == a.Wo;
+  auto out_row = [&](long m) -> uint32_t {  // output pixel of GEMM row m
+    if (dense) return (uint32_t)m;
+    const int mi = (int)m, hw = a.Ho * a.Wo;
+    const int n = mi / hw, rem = mi - n * hw;
+    const int oh = rem / a.Wo, ow = rem - oh * a.Wo;
+    return (uint32_t)((n * a.Hout + oh * a.OS + a.oy) * a.Wout + ow * a.OS + a.ox);
+  };
   float sv[8], tv[8];
   constexpr bool GELU = EPI == kEpiGeluFwd || EPI == kEpiGeluBwd;
   uint64_t dseed = 0;
@@ -330,6 +349,42 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
   float q0[8], q1[8], q2[8];
 #pragma unroll
   for (int k = 0; k < 8; ++k) { q0[k] = 0.f; q1[k] = 0.f; q2[k] = 0.f; }
+  // ---- operand prefetch (PF > 0): registers of one group of PF sweeps
+  constexpr int PFN = PF > 0 ? PF : 1;
+  uint4 pfo[PFN], pfx[PFN], pfb[PFN];
+  uint32_t pfm[PFN];
+  auto prefetch = [&](int j, int sw0) {
+    // Descriptors of the tensors' REAL sizes (the join backward is a dense stride-1 data gradient:
+    // out, ex and jyb are [M][Cout], the mask a bit per element), not the 4 GiB one of the output
+    // stores: the range check is made per dword against the record count, and under 0xFFFFFFFF
+    // records the first three dwords at kOOB would be in range -- a read 4 GiB past the tensor.
+    // The launcher keeps these sizes below kOOB (x1_launch_tile).
+    const int obytes = (int)(a.M * a.Cout * 2);
+    const __amdgpu_buffer_rsrc_t rl = __builtin_amdgcn_make_buffer_rsrc((void*)a.out, (short)0, obytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.ex, (short)0, obytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rb = __builtin_amdgcn_make_buffer_rsrc(
+        (void*)(a.jyb != nullptr ? a.jyb : a.ex), (short)0, obytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rm = __builtin_amdgcn_make_buffer_rsrc((void*)a.jmask, (short)0, obytes >> 4, 0x00020000);
+#pragma unroll
+    for (int s = 0; s < PFN; ++s) {
+      const int lr = rs + (sw0 + s) * RPS;
+      const long m = m0 + pix(lr >> 5, j, lr & 31);
+      const bool ok = ew && m < a.M;
+      const uint32_t e = out_row(m) * (uint32_t)a.Cout + c;
+      pfo[s] = ld_buf16(rl, ok ? e * 2u : kOOB);
+      pfx[s] = ld_buf16(rx, ok ? e * 2u : kOOB);
+      pfb[s] = ld_buf16(rb, ok && a.jyb != nullptr ? e * 2u : kOOB);
+      pfm[s] = __builtin_amdgcn_raw_buffer_load_b8(rm, ok ? e >> 3 : kOOB, 0, 0);
+    }
+  };
+  auto unpack8 = [](const uint4& u, float* f) {
+    const uint32_t w[4] = {u.x, u.y, u.z, u.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) { f[2 * q] = bf16_lo(w[q]); f[2 * q + 1] = bf16_hi(w[q]); }
+  };
+  // (the first pass's group is requested before the opening barrier, a later pass's before the
+  // barrier that frees the staging rows)
+  if constexpr (PF > 0) prefetch(0, 0);
   __syncthreads();  // every wave is done with the K tiles (and the split-K flag)
 #pragma unroll
   for (int j = 0; j < TM; ++j) {
@@ -357,19 +412,13 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
     // ---- rows of this pass: 8 channels x NSW rows per thread
 #pragma unroll
     for (int sw = 0; sw < NSW; ++sw) {
+      if constexpr (PF > 0) {
+        if (sw > 0 && sw % PFN == 0) prefetch(j, sw);  // the pass's next group of sweeps
+      }
       const int lr = rs + sw * RPS;
       const long m = m0 + pix(lr >> 5, j, lr & 31);
       if (ew && m < a.M) {
-        uint32_t orow;
-        if (dense) {
-          orow = (uint32_t)m;
-        } else {
-          const int mi = (int)m, hw = a.Ho * a.Wo;
-          const int n = mi / hw, rem = mi - n * hw;
-          const int oh = rem / a.Wo, ow = rem - oh * a.Wo;
-          orow = (uint32_t)((n * a.Hout + oh * a.OS + a.oy) * a.Wout + ow * a.OS + a.ox);
-        }
-        const uint32_t e = orow * (uint32_t)a.Cout + c;
+        const uint32_t e = out_row(m) * (uint32_t)a.Cout + c;
         const float4 va = *reinterpret_cast<const float4*>(stg + lr * SW + cg * 8);
         const float4 vb = *reinterpret_cast<const float4*>(stg + lr * SW + cg * 8 + 4);
         float v[8] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w};
@@ -390,14 +439,21 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
           st_out(ro, e * 2u, a.out + e, v, a.wthru);
         } else if constexpr (EPI == kEpiJoinBwd) {
           float e8[8], ya[8], yb[8], o8[8];
-          Vec8<bf16>::load(a.out + e, e8);
-          Vec8<bf16>::load(a.ex + e, ya);
           const bool hb = a.jyb != nullptr;
-          if (hb) Vec8<bf16>::load(a.jyb + e, yb);
           uint32_t mk = 0;
-          if constexpr (ACT == kActRelu) mk = a.jmask[e >> 3];
-          else if (!zm) Vec8<bf16>::load(a.jout + e, o8);
-          else if (!hb) Vec8<bf16>::load(a.jx + e, o8);
+          if constexpr (PF > 0) {
+            unpack8(pfo[sw % PFN], e8);
+            unpack8(pfx[sw % PFN], ya);
+            if (hb) unpack8(pfb[sw % PFN], yb);
+            mk = pfm[sw % PFN];
+          } else {
+            Vec8<bf16>::load(a.out + e, e8);
+            Vec8<bf16>::load(a.ex + e, ya);
+            if (hb) Vec8<bf16>::load(a.jyb + e, yb);
+            if constexpr (ACT == kActRelu) mk = a.jmask[e >> 3];
+            else if (!zm) Vec8<bf16>::load(a.jout + e, o8);
+            else if (!hb) Vec8<bf16>::load(a.jx + e, o8);
+          }
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
             const float gv = v[k] + e8[k];
@@ -470,6 +526,9 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, f32x16 (&acc)[B
           st_out(ro, e * 2u, a.out + e, v, a.wthru);
         }
       }
+    }
+    if constexpr (PF > 0) {
+      if (j + 1 < TM) prefetch(j + 1, 0);
     }
     if (j + 1 < TM) __syncthreads();  // the next pass overwrites the staging rows
   }

@@ -51,7 +51,10 @@ __host__ __device__ constexpr size_t x1_ring_bytes(int BN) { return (size_t)kX1N
 __host__ __device__ constexpr size_t x1_stage_bytes(int BN) { return (size_t)64 * (BN + 4) * 4; }
 
 // NKT: K / 64 (the K loop is unrolled: the resident fragments are registers)
-template <int BM, int BN, int NKT, int PRO, int EPI, int ACT>
+// PF: the epilogue's operand prefetch depth (conv_epilogue).  Every prefetched load is requested
+// and consumed inside the epilogue, after the column tile's last counted wait: the vmcnt counts
+// of the weight ring are those of PF = 0.
+template <int BM, int BN, int NKT, int PRO, int EPI, int ACT, int PF = 0>
 __global__ __launch_bounds__(256, 2) void x1_kernel(const ConvArgs a, const int xn) {
   static_assert(PRO == kProNone || PRO == kProAffineAct || PRO == kProFold, "prologues: none, affine, fold");
   static_assert(ACT == kActNone || ACT == kActRelu, "activations: none, ReLU");
@@ -268,14 +271,15 @@ __global__ __launch_bounds__(256, 2) void x1_kernel(const ConvArgs a, const int 
       }
       cbuf = cbuf == kX1NB - 1 ? 0 : cbuf + 1;
     }
-    conv_epilogue<BM, BN, EPI, ACT, 256, 2, 2>(a, acc, m0, (col0 + ct) * BN, bm, tid, stg, red, true, 1.f);
+    conv_epilogue<BM, BN, EPI, ACT, 256, 2, 2, PixLinear, PF>(a, acc, m0, (col0 + ct) * BN, bm, tid, stg, red, true,
+                                                              1.f);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (the zero chunks past the last tile)
 }
 
-template <int BM, int BN, int NKT, int PRO, int EPI, int ACT>
+template <int BM, int BN, int NKT, int PRO, int EPI, int ACT, int PF = 0>
 void x1_launch_one(const ConvArgs& a, int xn, size_t lds, hipStream_t st) {
-  auto kern = x1_kernel<BM, BN, NKT, PRO, EPI, ACT>;
+  auto kern = x1_kernel<BM, BN, NKT, PRO, EPI, ACT, PF>;
   static size_t attr_set = 64 * 1024;  // default dynamic-LDS limit; raise only when needed
   if (lds > attr_set) {
     FDT_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -291,6 +295,16 @@ void x1_launch_one(const ConvArgs& a, int xn, size_t lds, hipStream_t st) {
 template <int PRO, int EPI, int ACT>
 bool x1_launch_tile(const ConvArgs& a, int BM, int BN, int xn, size_t lds, hipStream_t st) {
   if (BN != 128) return false;
+  if constexpr (EPI == kEpiJoinBwd && ACT == kActRelu) {
+    // the epilogue's operand prefetch (set_conv_epi_prefetch): a whole pass (4 sweeps).  Not at
+    // K = 256: beside the 128 resident-fragment VGPRs even groups of 2 sweeps spill (28 VGPRs)
+    // (its descriptors carry the output's byte size, which must stay below the kOOB offset)
+    if (conv_epi_prefetch() && a.M * a.Cout * 2 < 0x7FFFFFF0L) {
+      if (BM == 128 && a.K == 64) { x1_launch_one<128, 128, 1, PRO, EPI, ACT, 4>(a, xn, lds, st); return true; }
+      if (BM == 128 && a.K == 128) { x1_launch_one<128, 128, 2, PRO, EPI, ACT, 4>(a, xn, lds, st); return true; }
+      if (BM == 64 && a.K == 512) { x1_launch_one<64, 128, 8, PRO, EPI, ACT, 4>(a, xn, lds, st); return true; }
+    }
+  }
   if (BM == 128 && a.K == 64) { x1_launch_one<128, 128, 1, PRO, EPI, ACT>(a, xn, lds, st); return true; }
   if (BM == 128 && a.K == 128) { x1_launch_one<128, 128, 2, PRO, EPI, ACT>(a, xn, lds, st); return true; }
   if (BM == 128 && a.K == 256) { x1_launch_one<128, 128, 4, PRO, EPI, ACT>(a, xn, lds, st); return true; }

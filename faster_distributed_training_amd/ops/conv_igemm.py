@@ -334,6 +334,17 @@ def _is_pure(shp):
     return shp.k == 1 and shp.stride == 1 and shp.pad == 0
 
 
+# Operand prefetch of the join-backward epilogue on the stationary 1x1 kernel (conv_epilogue's PF,
+# csrc/kernels/conv_igemm_impl.h): a pass's reads of the incoming gradient, the branch outputs and
+# the mask are requested before that pass's staging instead of sweep by sweep.  Same bits either
+# way; FDT_EPI_PREFETCH=0 launches the load-per-sweep instantiations (A/B, profiles/x7/README.md).
+def epi_prefetch_default(env=None) -> bool:
+    return (os.environ if env is None else env).get("FDT_EPI_PREFETCH", "1") != "0"
+
+
+EPI_PREFETCH = epi_prefetch_default()
+
+
 def _kg(ent, kg, tile3, ns, K, pro=None, x1=None):
     """K groups of one launch: explicit ``kg``, else the tuned entry's, else 1 (3 = the
     LDS-DMA ring, prologue-free launches only; 10 = the stationary 1x1 loop -- an entry's
@@ -620,6 +631,8 @@ def conv_dgrad(g, y, al, be, wd, shp: ConvShape, x_shape, epi=EPI_STORE, out=Non
         _log("dgrad", N, Hx, shp, ent, (bm, bn, bk), ns, kgv)
         if kgv == X1_KG:  # (the native nsplit argument carries xn)
             ns, slab_p, cnt_p = xnv, 0, 0
+            if epi == EPI_JOINBWD:
+                nat.set_conv_epi_prefetch(EPI_PREFETCH)
         assert gs is None or pro == PRO_FOLD, "gs needs the fold prologue (al/be)"
         nat.conv_igemm(g.data_ptr(), _p(y) if pro == PRO_FOLD else 0, _p(al), _p(be), _p(gs), wd.data_ptr(),
                        out.data_ptr(), _p(part) if epi in (EPI_ACTBWD, EPI_JOINBWD) else 0,
