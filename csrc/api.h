@@ -136,6 +136,16 @@ void colsum_bf16(uint64_t x, uint64_t out, long rows, int cols, long ld, uint64_
 void slab_sum_acc(uint64_t src, uint64_t dst, int s, long ld, long n, uint64_t stream);
 void relu_bwd_colsum(uint64_t gact, uint64_t pre, uint64_t gpre, uint64_t gb, long rows, int cols, int dt,
                      uint64_t stream);
+// linear_wgrad.hip: split-K weight gradient of a linear layer, slab [nsplit][out][in] fp32 =
+// per-split gy^T x for bf16 gy [M][out], x [M][in] (contiguous); bslab [nsplit][out] = per-split
+// column sums of gy (0 = none).  nsplit = 0: the launcher's own choice (linear_wgrad_splits).
+bool linear_wgrad_supported(long M, int out, int in);
+int linear_wgrad_splits(long M, int out, int in);
+void linear_wgrad(uint64_t gy, uint64_t x, uint64_t slab, uint64_t bslab, long M, int out, int in, int nsplit,
+                  uint64_t stream);
+// dst[c] += sum over splits of bslab[s * ld + c], c < n, in split order
+void linear_bias_fold(uint64_t bslab, uint64_t dst, int nsplit, int ld, int n, uint64_t stream);
+int linear_wgrad_chunk(int kc);  // tokens per staged chunk (64 or 128): set (kc > 0), returns the previous
 // augment.hip
 void augment(uint64_t src, uint64_t idx, uint64_t labels_src, uint64_t labels_out, uint64_t out, int B, int H, int W,
              int C, int Cout, int pad, int do_flip, uint64_t rng, float m0, float m1, float m2, float s0, float s1,

@@ -12,10 +12,16 @@ slices written in fp32 (``out_dtype``) and summed: 35-76 us per call, and dW com
 fp32 straight for the fp32 master gradient (no bf16 rounding of the gradient, no cast).
 Forward and the data gradient stay single library GEMMs (their M = tokens is large).
 
+With ``FDT_LINEAR_WGRAD`` (``wgrad_backend``) the slices come from the project's own split-K
+MFMA kernel instead (csrc/kernels/linear_wgrad.hip): fp32 from end to end, no atomics, and the
+bias gradient's column sums taken from the dY tiles the kernel has staged anyway.
+
 Reference: the projections are plain ``nn.Linear`` (``transformer.py:159-227``); parameters
 and state-dict names are unchanged -- only the autograd formula is replaced.
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn.functional as F
@@ -28,8 +34,72 @@ def _splits(M: int) -> int:
     return 1
 
 
+# (M, out, in) for which FDT_LINEAR_WGRAD=auto takes the HIP kernel: the rows of the per-call
+# table of profiles/linear_wgrad/README.md where it is faster than the bmm path by more than
+# the run-to-run spread of either (nothing unmeasured is switched over).
+_AUTO_HIP = {(32768, 1536, 512), (32768, 512, 512), (32768, 1024, 512), (65536, 1024, 512)}
+
+
+def _auto_hip(M: int, out: int, in_: int) -> bool:
+    return (M, out, in_) in _AUTO_HIP
+
+
+def wgrad_backend(M: int, out: int, in_: int, dtype, device="cuda") -> str:
+    """"hip" when dW = gy^T x for gy [M, out], x [M, in] of ``dtype`` on ``device`` runs through
+    linear_wgrad.hip, "library" when through the strided-batched library GEMM.  The one place
+    that decides; ``FDT_LINEAR_WGRAD`` = 0 (never), 1 (wherever supported) or auto."""
+    from . import _native
+    mode = os.environ.get("FDT_LINEAR_WGRAD", "auto")
+    if mode not in ("0", "1", "auto"):
+        raise ValueError(f"FDT_LINEAR_WGRAD={mode!r}: expected 0, 1 or auto")
+    if mode == "0" or dtype != torch.bfloat16 or torch.device(device).type != "cuda" or not _native.enabled():
+        return "library"
+    if not _native.native().linear_wgrad_supported(M, out, in_):
+        return "library"
+    return "hip" if mode == "1" or _auto_hip(M, out, in_) else "library"
+
+
+def _hip_ok(gy: torch.Tensor, x: torch.Tensor) -> bool:
+    return (gy.dtype == x.dtype == torch.bfloat16 and gy.is_contiguous() and x.is_contiguous()
+            and gy.data_ptr() % 16 == 0 and x.data_ptr() % 16 == 0
+            and wgrad_backend(gy.shape[0], gy.shape[1], x.shape[1], gy.dtype, gy.device) == "hip")
+
+
+def wgrad_slabs(gy: torch.Tensor, x: torch.Tensor, nsplit: int = 0, bias: bool = False):
+    """The HIP kernel's per-split partials of gy^T x: fp32 [nsplit, out, in], and (``bias``) of
+    gy's column sums: fp32 [nsplit, out] or None.  nsplit = 0: the launcher's choice."""
+    from . import _native
+    nat = _native.native()
+    M, out = gy.shape
+    in_ = x.shape[1]
+    if gy.dtype != torch.bfloat16 or x.dtype != torch.bfloat16 or x.shape[0] != M \
+            or not (gy.is_cuda and x.is_cuda and gy.is_contiguous() and x.is_contiguous()):
+        raise ValueError("wgrad_slabs: contiguous bf16 GPU operands [M, out], [M, in]")
+    s = nsplit or nat.linear_wgrad_splits(M, out, in_)
+    slab = torch.empty(s, out, in_, device=gy.device, dtype=torch.float32)
+    bslab = torch.empty(s, out, device=gy.device, dtype=torch.float32) if bias else None
+    nat.linear_wgrad(gy.data_ptr(), x.data_ptr(), slab.data_ptr(), _native.ptr(bslab), M, out, in_, s,
+                     _native.stream_ptr())
+    return slab, bslab
+
+
+def _fold_new(slab: torch.Tensor) -> torch.Tensor:
+    out = torch.zeros(slab.shape[1:], device=slab.device, dtype=torch.float32)
+    slab_sum_into(slab, out)
+    return out
+
+
+def bias_fold_into(bslab: torch.Tensor, dst: torch.Tensor, col0: int = 0) -> None:
+    """dst += sum over splits of bslab[:, col0 : col0 + dst.numel()], in split order."""
+    from . import _native
+    _native.native().linear_bias_fold(bslab.data_ptr() + 4 * col0, dst.data_ptr(), bslab.shape[0], bslab.shape[1],
+                                      dst.numel(), _native.stream_ptr())
+
+
 def wgrad(gy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
     """dW = gy^T x in fp32 for gy [M, out], x [M, in] (bf16 on the GPU)."""
+    if _hip_ok(gy, x):
+        return _fold_new(wgrad_slabs(gy, x)[0])
     M = gy.shape[0]
     s = _splits(M)
     try:
@@ -105,6 +175,9 @@ def mark_ready(p) -> None:
 
 def wgrad_into(gy: torch.Tensor, x: torch.Tensor, dst: torch.Tensor) -> None:
     """dst += gy^T x (fp32 dst): split-K slabs folded into dst by one kernel."""
+    if _hip_ok(gy, x):
+        slab_sum_into(wgrad_slabs(gy, x)[0], dst)
+        return
     M = gy.shape[0]
     s = _splits(M)
     if s > 1 and _native_ok(dst):
@@ -165,14 +238,34 @@ class _Linear(torch.autograd.Function):
         if ctx.needs_input_grad[0]:
             dx = (g2 @ wc).view(xc.shape).to(xd)
         w, b = ctx.params
-        if ctx.needs_input_grad[1]:
+        want_b = bd is not None and ctx.needs_input_grad[2] and ctx.bias_grad
+        bslab = None
+        if ctx.needs_input_grad[1] and _hip_ok(g2, x2):
+            # the HIP kernel: its slabs folded as below, the bias partials from the same pass
+            slab, bslab = wgrad_slabs(g2, x2, bias=want_b)
+            tgt = direct_target(w)
+            if tgt is not None:
+                slab_sum_into(slab, tgt)
+                mark_ready(w)
+            else:
+                dw = _fold_new(slab).to(wd)
+        elif ctx.needs_input_grad[1]:
             tgt = direct_target(w)
             if tgt is not None:
                 wgrad_into(g2, x2, tgt)
                 mark_ready(w)
             else:
                 dw = wgrad(g2, x2).to(wd)
-        if bd is not None and ctx.needs_input_grad[2] and ctx.bias_grad:
+        if bslab is not None:
+            tgt = direct_target(b)
+            if tgt is not None:
+                bias_fold_into(bslab, tgt)
+                mark_ready(b)
+            else:
+                db = torch.zeros(bslab.shape[1], device=bslab.device, dtype=torch.float32)
+                bias_fold_into(bslab, db)
+                db = db.to(bd)
+        elif want_b:
             tgt = direct_target(b)
             if tgt is not None:
                 bias_grad_into(g2, tgt)
@@ -243,15 +336,19 @@ class _LinearCat(torch.autograd.Function):
         rows = [w.shape[0] for w in ws]
         offs = [sum(rows[:i]) for i in range(n)]
         gw = [None] * n
+        slab = bslab = None
         if any(ctx.needs_input_grad[3:3 + n]):
             tg = [direct_target(w) for w in ws]
             M, K, R = g2.shape[0], x2.shape[1], wc.shape[0]
             s = _splits(M)
+            if _hip_ok(g2, x2):  # the HIP kernel's slabs (and bias partials) instead of the bmm's
+                slab, bslab = wgrad_slabs(g2, x2, bias=any(ctx.needs_input_grad[3 + n:]))
+                s = slab.shape[0]
             done = False
-            if all(t is not None for t in tg) and s > 1 and _native_ok(g2) and K % 4 == 0:
+            if all(t is not None for t in tg) and (s > 1 or slab is not None) and _native_ok(g2) and K % 4 == 0:
                 try:
-                    p = torch.bmm(g2.view(s, M // s, -1).transpose(1, 2), x2.view(s, M // s, -1),
-                                  out_dtype=torch.float32)
+                    p = slab if slab is not None else torch.bmm(
+                        g2.view(s, M // s, -1).transpose(1, 2), x2.view(s, M // s, -1), out_dtype=torch.float32)
                     if all(tg[i + 1].data_ptr() == tg[i].data_ptr() + rows[i] * K * 4 for i in range(n - 1)):
                         # the parameters' gradients are adjacent (utils/flat.py flat_adjacent): one pass
                         _native.native().slab_sum_acc(p.data_ptr(), tg[0].data_ptr(), s, R * K, R * K,
@@ -267,7 +364,7 @@ class _LinearCat(torch.autograd.Function):
                 for w in ws:
                     mark_ready(w)
             else:
-                dw = wgrad(g2, x2)
+                dw = _fold_new(slab) if slab is not None else wgrad(g2, x2)
                 for i, w in enumerate(ws):
                     part = dw[offs[i]:offs[i] + rows[i]]
                     if tg[i] is not None:
@@ -281,7 +378,15 @@ class _LinearCat(torch.autograd.Function):
                 continue
             cols = g2[:, offs[i]:offs[i] + rows[i]]
             tgt = direct_target(b)
-            if tgt is not None:
+            if bslab is not None:  # this parameter's column range of the kernel's partials
+                if tgt is None:
+                    gb[i] = torch.zeros(rows[i], device=bslab.device, dtype=torch.float32)
+                bias_fold_into(bslab, tgt if tgt is not None else gb[i], offs[i])
+                if tgt is not None:
+                    mark_ready(b)
+                else:
+                    gb[i] = gb[i].to(b.dtype)
+            elif tgt is not None:
                 bias_grad_into(cols, tgt)
                 mark_ready(b)
             else:

@@ -4,6 +4,7 @@ GEMM PyTorch's autograd issues, a split-K batched GEMM, and the MFMA wgrad kerne
 conv engine (1x1 "direct" mode: split-K with fp32 atomics straight into the fp32 gradient).
 
     python scripts/bench_linear_wgrad.py [--tokens 32768]
+    python scripts/bench_linear_wgrad.py --table      # per-call table: linear_wgrad.hip vs the bmm path
 """
 import argparse
 import os
@@ -26,10 +27,69 @@ def timeit(fn, iters=20):
     return a.elapsed_time(b) / iters * 1e3  # us
 
 
+def graph_time(fn, replays=50, repeats=5):
+    """us per call of fn under graph replay: (median, min, max) over `repeats` windows."""
+    fn()
+    torch.cuda.synchronize()
+    st = torch.cuda.Stream()
+    st.wait_stream(torch.cuda.current_stream())
+    gr = torch.cuda.CUDAGraph()
+    with torch.cuda.stream(st):
+        fn()
+        with torch.cuda.graph(gr, stream=st):
+            fn()
+    torch.cuda.synchronize()
+    ts = sorted(timeit(gr.replay, replays) for _ in range(repeats))
+    return ts[len(ts) // 2], ts[0], ts[-1]
+
+
+def table(chunks=(64, 128)):
+    """Weight + bias gradient into fp32 targets, per call: the library path (bmm slices, slab_sum_acc,
+    colsum_bf16) against linear_wgrad.hip (kernel, slab_sum_acc, linear_bias_fold)."""
+    from faster_distributed_training_amd.ops import _native, linear as L
+    nat = _native.native()
+    dev = torch.device("cuda")
+    for M in (65536, 32768, 8192, 4096):
+        for fin, fout in [(512, 1536), (512, 512), (512, 1024), (1024, 512)]:
+            x = torch.randn(M, fin, device=dev).to(torch.bfloat16)
+            g = torch.randn(M, fout, device=dev).to(torch.bfloat16)
+            dw = torch.zeros(fout, fin, device=dev)
+            db = torch.zeros(fout, device=dev)
+            s = L._splits(M)
+
+            def lib():
+                p = torch.bmm(g.view(s, M // s, fout).transpose(1, 2), x.view(s, M // s, fin), out_dtype=torch.float32)
+                L.slab_sum_into(p, dw)
+                L.bias_grad_into(g, db)
+
+            def hip(ns=0):
+                slab, bslab = L.wgrad_slabs(g, x, ns, bias=True)
+                L.slab_sum_into(slab, dw)
+                L.bias_fold_into(bslab, db)
+
+            def kern(ns=0):
+                L.wgrad_slabs(g, x, ns, bias=True)
+
+            row = {"M": M, "in": fin, "out": fout, "library_us": [round(t, 1) for t in graph_time(lib)]}
+            for kc in chunks:
+                nat.linear_wgrad_chunk(kc)
+                ns0 = nat.linear_wgrad_splits(M, fout, fin)
+                for ns in sorted({ns0, max(1, ns0 // 2), ns0 * 2}):
+                    t = graph_time(lambda: hip(ns))
+                    tk = graph_time(lambda: kern(ns))
+                    row[f"hip_kc{kc}_s{ns}{'*' if ns == ns0 else ''}_us"] = [round(v, 1) for v in t]
+                    row[f"kernel_kc{kc}_s{ns}_us"] = round(tk[0], 1)
+            nat.linear_wgrad_chunk(64)
+            print(row, flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--tokens", type=int, default=32768)
+    ap.add_argument("--table", action="store_true")
     a = ap.parse_args()
+    if a.table:
+        return table()
     from faster_distributed_training_amd.ops import conv_igemm as ci
     dev = torch.device("cuda")
     M = a.tokens
