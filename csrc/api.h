@@ -146,6 +146,12 @@ void linear_wgrad(uint64_t gy, uint64_t x, uint64_t slab, uint64_t bslab, long M
 // dst[c] += sum over splits of bslab[s * ld + c], c < n, in split order
 void linear_bias_fold(uint64_t bslab, uint64_t dst, int nsplit, int ld, int n, uint64_t stream);
 int linear_wgrad_chunk(int kc);  // tokens per staged chunk (64 or 128): set (kc > 0), returns the previous
+// linear_gemm.hip: dense bf16 GEMM of a linear layer, out [M][N] (contiguous, fp32 accumulation).
+// kind 0 (nt, forward): a [M][K] . w [N][K]^T + bias [N] (0 = none); kind 1 (nn, data gradient):
+// a [M][K] . w [K][N].  N, K multiples of 128.
+bool linear_gemm_supported(long M, int N, int K);
+void linear_gemm(uint64_t a, uint64_t w, uint64_t bias, uint64_t out, long M, int N, int K, int kind,
+                 uint64_t stream);
 // augment.hip
 void augment(uint64_t src, uint64_t idx, uint64_t labels_src, uint64_t labels_out, uint64_t out, int B, int H, int W,
              int C, int Cout, int pad, int do_flip, uint64_t rng, float m0, float m1, float m2, float s0, float s1,

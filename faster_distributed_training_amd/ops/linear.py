@@ -16,6 +16,10 @@ With ``FDT_LINEAR_WGRAD`` (``wgrad_backend``) the slices come from the project's
 MFMA kernel instead (csrc/kernels/linear_wgrad.hip): fp32 from end to end, no atomics, and the
 bias gradient's column sums taken from the dY tiles the kernel has staged anyway.
 
+With ``FDT_LINEAR_GEMM`` (``gemm_backend``) the forward ``x W^T + b`` and the data gradient
+``dY W`` run through the project's own dense MFMA GEMM (csrc/kernels/linear_gemm.hip, ``gemm``)
+instead of the library's; ``auto``, the default, takes it only for measured-faster shapes.
+
 Reference: the projections are plain ``nn.Linear`` (``transformer.py:159-227``); parameters
 and state-dict names are unchanged -- only the autograd formula is replaced.
 """
@@ -111,6 +115,71 @@ def wgrad(gy: torch.Tensor, x: torch.Tensor) -> torch.Tensor:
         if s == 1:
             return (gy.t() @ x).float()
         return torch.bmm(gy.view(s, M // s, -1).transpose(1, 2), x.view(s, M // s, -1)).float().sum(0)
+
+
+# ------------------------------------------------------------------ forward / data-gradient GEMM
+# (kind, M, N, K) for which FDT_LINEAR_GEMM=auto takes the HIP kernel: the rows of the per-call table
+# of profiles/linear_gemm/README.md where it is faster than the library GEMM by more than the
+# run-to-run spread of either.  Empty: no measured row is.
+_AUTO_GEMM: set = set()
+
+_KINDS = {"nt": 0, "nn": 1}
+
+
+def gemm_backend(kind: str, M: int, N: int, K: int, dtype, device="cuda") -> str:
+    """"hip" when the [M, N] product of kind "nt" (a [M, K] . w [N, K]^T + bias: the forward) or "nn"
+    (a [M, K] . w [K, N]: the data gradient) of ``dtype`` on ``device`` runs through linear_gemm.hip,
+    "library" when through the library GEMM.  The one place that decides; ``FDT_LINEAR_GEMM`` = 0
+    (never), 1 (wherever supported) or auto (the measured rows of ``_AUTO_GEMM``)."""
+    from . import _native
+    mode = os.environ.get("FDT_LINEAR_GEMM", "auto")
+    if mode not in ("0", "1", "auto"):
+        raise ValueError(f"FDT_LINEAR_GEMM={mode!r}: expected 0, 1 or auto")
+    if kind not in _KINDS:
+        raise ValueError(f"gemm kind {kind!r}: expected nt or nn")
+    if mode == "0" or dtype != torch.bfloat16 or torch.device(device).type != "cuda" or not _native.enabled():
+        return "library"
+    if mode == "auto" and (kind, M, N, K) not in _AUTO_GEMM:
+        return "library"
+    return "hip" if _native.native().linear_gemm_supported(M, N, K) else "library"
+
+
+def _gemm_ok(a: torch.Tensor, w: torch.Tensor, bias, kind: str) -> bool:
+    ts = (a, w) if bias is None else (a, w, bias)
+    if not all(t.dtype == torch.bfloat16 and t.is_contiguous() and t.data_ptr() % 16 == 0 for t in ts):
+        return False
+    N = w.shape[0] if kind == "nt" else w.shape[1]
+    return a.dim() == 2 and gemm_backend(kind, a.shape[0], N, a.shape[1], a.dtype, a.device) == "hip"
+
+
+def gemm(a: torch.Tensor, w: torch.Tensor, bias: torch.Tensor | None = None, kind: str = "nt") -> torch.Tensor:
+    """The HIP kernel's bf16 [M, N] product of contiguous bf16 GPU operands: kind "nt" a [M, K] .
+    w [N, K]^T (+ bias [N]), kind "nn" a [M, K] . w [K, N].  Launched on the current stream; the
+    output is the only allocation and nothing synchronises (graph-capture safe)."""
+    from . import _native
+    M, K = a.shape
+    N, Kw = (w.shape[0], w.shape[1]) if kind == "nt" else (w.shape[1], w.shape[0])
+    ts = (a, w) if bias is None else (a, w, bias)
+    if kind not in _KINDS or Kw != K or (bias is not None and (kind != "nt" or bias.shape != (N,))) \
+            or not all(t.dtype == torch.bfloat16 and t.is_cuda and t.is_contiguous() for t in ts):
+        raise ValueError("gemm: contiguous bf16 GPU operands a [M, K], w [N, K] (nt, + bias [N]) or [K, N] (nn)")
+    out = torch.empty(M, N, device=a.device, dtype=torch.bfloat16)
+    _native.native().linear_gemm(a.data_ptr(), w.data_ptr(), _native.ptr(bias), out.data_ptr(), M, N, K,
+                                 _KINDS[kind], _native.stream_ptr())
+    return out
+
+
+def _forward(xc: torch.Tensor, wc: torch.Tensor, bc) -> torch.Tensor:
+    """F.linear(xc, wc, bc), through the HIP kernel on the 2-D token view when gemm_backend says so."""
+    x2 = xc.reshape(-1, xc.shape[-1])
+    if _gemm_ok(x2, wc, bc, "nt"):
+        return gemm(x2, wc, bc, "nt").view(*xc.shape[:-1], wc.shape[0])
+    return F.linear(xc, wc, bc)
+
+
+def _dgrad(g2: torch.Tensor, wc: torch.Tensor) -> torch.Tensor:
+    """g2 @ wc for g2 [M, out], wc [out, in]."""
+    return gemm(g2, wc, None, "nn") if _gemm_ok(g2, wc, None, "nn") else g2 @ wc
 
 
 # ------------------------------------------------------------------ direct gradients
@@ -221,7 +290,7 @@ class _Linear(torch.autograd.Function):
         xin_dtype = x.dtype
         xc = x.to(dt)
         wc = cast_weight(w, dt)
-        y = F.linear(xc, wc, None if b is None else cast_weight(b, dt))
+        y = _forward(xc, wc, None if b is None else cast_weight(b, dt))
         ctx.save_for_backward(xc, wc)
         ctx.meta = (xin_dtype, w.dtype, None if b is None else b.dtype)
         ctx.params = (w, b)  # leaves whose gradient may be written in place (direct_target)
@@ -236,7 +305,7 @@ class _Linear(torch.autograd.Function):
         x2 = xc.reshape(-1, xc.shape[-1])
         dx = dw = db = None
         if ctx.needs_input_grad[0]:
-            dx = (g2 @ wc).view(xc.shape).to(xd)
+            dx = _dgrad(g2, wc).view(xc.shape).to(xd)
         w, b = ctx.params
         want_b = bd is not None and ctx.needs_input_grad[2] and ctx.bias_grad
         bslab = None
@@ -318,7 +387,7 @@ class _LinearCat(torch.autograd.Function):
         xc = x.to(dt)
         wc = stacked([cast_weight(w, dt) for w in ws])
         bc = stacked([cast_weight(b, dt) for b in bs]) if bs else None
-        y = F.linear(xc, wc, bc)
+        y = _forward(xc, wc, bc)
         ctx.save_for_backward(xc, wc)
         ctx.params = (ws, bs)
         ctx.xd = x.dtype
@@ -332,7 +401,7 @@ class _LinearCat(torch.autograd.Function):
         n = len(ws)
         g2 = gy.reshape(-1, gy.shape[-1]).to(wc.dtype)
         x2 = xc.reshape(-1, xc.shape[-1])
-        dx = (g2 @ wc).view(xc.shape).to(ctx.xd) if ctx.needs_input_grad[0] else None
+        dx = _dgrad(g2, wc).view(xc.shape).to(ctx.xd) if ctx.needs_input_grad[0] else None
         rows = [w.shape[0] for w in ws]
         offs = [sum(rows[:i]) for i in range(n)]
         gw = [None] * n
