@@ -133,6 +133,10 @@ void embedding_bwd(uint64_t g, uint64_t ids, uint64_t types, uint64_t pos_ids, u
 // mlp.hip
 void bias_relu_fwd(uint64_t pre, uint64_t b, uint64_t act, long rows, int cols, int dt, uint64_t stream);
 void colsum_bf16(uint64_t x, uint64_t out, long rows, int cols, long ld, uint64_t stream);
+// per-row-block column sums without atomics: slab [colsum_bf16_blocks(rows, cols)][cols] fp32 (fold:
+// linear_bias_fold, in block order)
+int colsum_bf16_blocks(long rows, int cols);
+void colsum_bf16_slab(uint64_t x, uint64_t slab, long rows, int cols, uint64_t stream);
 void slab_sum_acc(uint64_t src, uint64_t dst, int s, long ld, long n, uint64_t stream);
 void relu_bwd_colsum(uint64_t gact, uint64_t pre, uint64_t gpre, uint64_t gb, long rows, int cols, int dt,
                      uint64_t stream);
@@ -152,6 +156,12 @@ int linear_wgrad_chunk(int kc);  // tokens per staged chunk (64 or 128): set (kc
 bool linear_gemm_supported(long M, int N, int K);
 void linear_gemm(uint64_t a, uint64_t w, uint64_t bias, uint64_t out, long M, int N, int K, int kind,
                  uint64_t stream);
+// The same GEMM finished through the FFN's GELU-dropout epilogues (mask: dropout_math.h keep8 of the
+// flat [M][N] index).  kind 0: act = a = a_op . w^T + bias (bf16 bias, required), out = h =
+// keep * gelu(a) / (1 - p).  kind 1: out = ga = keep * gelu'(act) * (a_op . w) / (1 - p) from the fp32
+// accumulator, gbslab [ceil(M / 128)][N] fp32 = per-panel column sums of ga (fold: linear_bias_fold).
+void linear_gemm_gelu(uint64_t a, uint64_t w, uint64_t bias, uint64_t act, uint64_t out, uint64_t gbslab, long M,
+                      int N, int K, int kind, float p, uint64_t seed, uint64_t seed_ptr, uint64_t stream);
 // augment.hip
 void augment(uint64_t src, uint64_t idx, uint64_t labels_src, uint64_t labels_out, uint64_t out, int B, int H, int W,
              int C, int Cout, int pad, int do_flip, uint64_t rng, float m0, float m1, float m2, float s0, float s1,

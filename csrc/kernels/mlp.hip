@@ -44,7 +44,9 @@ __global__ __launch_bounds__(256) void relu_bwd_colsum_kernel(const T* __restric
 // out[c] += sum_r x[r][c] for bf16 x [rows][cols] (cols % 8 == 0), fp32 out zeroed by the
 // caller: the bias gradient of a linear layer.  Lane = 8 adjacent columns (one 16-B load);
 // a 256-thread block covers (256 / lanes_per_row) rows x cols_blk columns of a row chunk,
-// folds its rows in registers + LDS, one atomic per column per block.
+// folds its rows in registers + LDS, one atomic per column per block.  SLAB: the block stores its
+// sums to out[blockIdx.y][cols] instead (no atomics; linear_bias_fold adds the row blocks in order).
+template <bool SLAB>
 __global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16* __restrict__ x, float* __restrict__ out,
                                                           long rows, int cols, long ld, int rows_per_blk) {
   __shared__ float red[256 * 8];
@@ -74,8 +76,17 @@ __global__ __launch_bounds__(256) void colsum_bf16_kernel(const bf16* __restrict
     float s = 0.f;
 #pragma unroll
     for (int l = 0; l < 8; ++l) s += red[(l * 32 + col / 8) * 8 + (col % 8)];
-    atomicAdd(out + blockIdx.x * 256 + col, s);
+    if constexpr (SLAB) out[(long)blockIdx.y * cols + blockIdx.x * 256 + col] = s;
+    else atomicAdd(out + blockIdx.x * 256 + col, s);
   }
+}
+
+// rows per block of the column-sum grid: ~512 workgroups in total, >= 64 rows per block
+static long colsum_rpb(long rows, int cols) {
+  const int cblk = (cols / 8 + 31) / 32;
+  long rpb = rows * cblk / 512;
+  if (rpb < 64) rpb = 64;
+  return (rpb + 7) / 8 * 8;
 }
 
 void colsum_bf16(uint64_t x, uint64_t out, long rows, int cols, long ld, uint64_t stream) {
@@ -83,12 +94,28 @@ void colsum_bf16(uint64_t x, uint64_t out, long rows, int cols, long ld, uint64_
   FDT_CHECK(cols % 8 == 0 && ld % 8 == 0 && ld >= cols && x % 16 == 0, "colsum_bf16: cols, ld % 8 == 0, 16-B aligned rows");
   if (rows == 0 || cols == 0) return;
   const int cblk = (cols / 8 + 31) / 32;
-  // ~512 workgroups in total, >= 64 rows per block
-  long rpb = rows * cblk / 512;
-  if (rpb < 64) rpb = 64;
-  rpb = (rpb + 7) / 8 * 8;
+  const long rpb = colsum_rpb(rows, cols);
   dim3 grid((unsigned)cblk, (unsigned)((rows + rpb - 1) / rpb));
-  colsum_bf16_kernel<<<grid, 256, 0, as_stream(stream)>>>(P<const bf16>(x), P<float>(out), rows, cols, ld, (int)rpb);
+  colsum_bf16_kernel<false><<<grid, 256, 0, as_stream(stream)>>>(P<const bf16>(x), P<float>(out), rows, cols, ld,
+                                                                 (int)rpb);
+  FDT_LAUNCH_CHECK();
+}
+
+int colsum_bf16_blocks(long rows, int cols) {
+  FDT_CHECK(rows >= 1 && cols >= 8 && cols % 8 == 0, "colsum_bf16_blocks: rows >= 1, cols % 8 == 0");
+  const long rpb = colsum_rpb(rows, cols);
+  return (int)((rows + rpb - 1) / rpb);
+}
+
+// slab [colsum_bf16_blocks(rows, cols)][cols] fp32 = per-row-block column sums of contiguous bf16 x
+void colsum_bf16_slab(uint64_t x, uint64_t slab, long rows, int cols, uint64_t stream) {
+  FDT_CHECK(rows >= 1 && cols >= 8 && cols % 8 == 0 && x % 16 == 0 && x != 0 && slab % 4 == 0 && slab != 0,
+            "colsum_bf16_slab: cols % 8 == 0, 16-B aligned rows, fp32 slab");
+  const int cblk = (cols / 8 + 31) / 32;
+  const long rpb = colsum_rpb(rows, cols);
+  dim3 grid((unsigned)cblk, (unsigned)((rows + rpb - 1) / rpb));
+  colsum_bf16_kernel<true><<<grid, 256, 0, as_stream(stream)>>>(P<const bf16>(x), P<float>(slab), rows, cols, cols,
+                                                                (int)rpb);
   FDT_LAUNCH_CHECK();
 }
 

@@ -15,6 +15,11 @@ tokens; ``csrc/kernels/conv_igemm_impl.h`` EPI_GELU_FWD / EPI_GELU_BWD):
   from the fp32 accumulator (``dL/dh`` is never rounded to bf16 or written) -- and the column
   sums of ``ga`` (``b_1``'s gradient) are reduced in the same epilogue (fp32 atomics).
 
+``FDT_FFN_FUSED=gemm`` (``KERNEL = "gemm"``) puts the same two epilogues on the dense MFMA GEMM of
+``ops/linear.py`` instead (``csrc/kernels/linear_gemm.hip`` ``linear_gemm_gelu``): its ``nn`` kind
+reads ``W_2`` as stored (no transposed copy per backward) and ``b_1``'s gradient comes from per-panel
+column sums folded in panel order (``linear_bias_fold``): no atomics, bitwise repeatable.
+
 The dropout mask is the counter hash of ``ops/dropout.py`` (same seed plumbing, so HIP-graph
 replays draw fresh masks).  ``W_2``'s GEMMs and ``W_1``'s weight / input gradients stay
 library GEMMs (hipBLASLt) or the split-K weight gradient of ``ops/linear.py``; parameters and
@@ -29,9 +34,13 @@ import torch.nn.functional as F
 
 from . import _native
 from .dropout import _seed
-from .linear import bias_grad, bias_grad_into, cast_weight, direct_target, mark_ready, wgrad, wgrad_into
+from .linear import (bias_fold_into, bias_grad, bias_grad_into, cast_weight, direct_target, mark_ready, wgrad,
+                     wgrad_into)
 
 FUSED = os.environ.get("FDT_FFN_FUSED", "0") != "0"  # default set from the A/B below
+# the kernel that carries the epilogues: "igemm" (FDT_FFN_FUSED=1, conv_igemm_impl.h) or "gemm"
+# (FDT_FFN_FUSED=gemm, linear_gemm.hip)
+KERNEL = "gemm" if os.environ.get("FDT_FFN_FUSED", "0") == "gemm" else "igemm"
 # which side runs on the fused kernel: the forward epilogue GEMM replaces a 45 us library GEMM +
 # a 46 us GELU-dropout pass with one ~76 us kernel, the backward one a library GEMM + the
 # GELU-dropout-backward/column-sum pass; FDT_FFN_FUSED_SIDES = fwd | bwd | both
@@ -44,9 +53,16 @@ TILE_BWD = (128, 128, 32, 1)
 
 
 def fusable(x: torch.Tensor, d_model: int, d_ff: int) -> bool:
+    if KERNEL not in ("igemm", "gemm"):
+        raise ValueError(f"ffn.KERNEL={KERNEL!r}: expected igemm or gemm")
     if not (FUSED and x.is_cuda and _native.use_native(x) and hasattr(_native.native(), "ffn_gemm")):
         return False
     dt = torch.get_autocast_dtype("cuda") if torch.is_autocast_enabled("cuda") else x.dtype
+    M = x.numel() // x.shape[-1]
+    if KERNEL == "gemm":
+        nat = _native.native()
+        return (dt == torch.bfloat16 and d_model % 128 == 0 and d_ff % 128 == 0 and M >= 4096
+                and nat.linear_gemm_supported(M, d_ff, d_model) and nat.linear_gemm_supported(M, d_model, d_ff))
     return (dt == torch.bfloat16 and d_model >= 8 and (d_model & (d_model - 1)) == 0 and d_ff % 128 == 0
             and x.numel() // x.shape[-1] >= 4096)
 
@@ -61,6 +77,30 @@ def _gemm(x, w, out, epi, bias=None, out2=None, a_in=None, gb=None, p=0.0, seed=
                               float(p), int(seed), int(sptr), bm, bn, bk, kg, _native.stream_ptr())
 
 
+def _gemm_gelu(x, w, kind, act, out, bias=None, gbslab=None, p=0.0, seed=0, sptr=0):
+    """linear_gemm.hip with a GELU-dropout epilogue.  kind 0: act = a = x w^T + bias, out = h;
+    kind 1: out = ga = keep * gelu'(act) * (x w) / (1 - p), gbslab [ceil(M / 128), N] = its column sums."""
+    M, K = x.shape
+    N = w.shape[0] if kind == 0 else w.shape[1]
+    ts = [t for t in (x, w, bias, act, out) if t is not None]
+    if not all(t.dtype == torch.bfloat16 and t.is_contiguous() for t in ts) or act.shape != (M, N) \
+            or out.shape != (M, N) or (gbslab is not None and gbslab.dtype != torch.float32):
+        raise ValueError("ffn gemm: contiguous bf16 operands, bias, a and output; fp32 column-sum slab")
+    _native.native().linear_gemm_gelu(x.data_ptr(), w.data_ptr(), _native.ptr(bias), act.data_ptr(), out.data_ptr(),
+                                      _native.ptr(gbslab), M, N, K, kind, float(p), int(seed), int(sptr),
+                                      _native.stream_ptr())
+
+
+def _colsum_into(g2, dst):
+    """dst += column sums of contiguous bf16 g2 [M, n] without atomics: per-row-block sums (mlp.hip
+    colsum_bf16_slab) folded in block order."""
+    nat = _native.native()
+    M, n = g2.shape
+    slab = torch.empty(nat.colsum_bf16_blocks(M, n), n, device=g2.device, dtype=torch.float32)
+    nat.colsum_bf16_slab(g2.data_ptr(), slab.data_ptr(), M, n, _native.stream_ptr())
+    bias_fold_into(slab, dst)
+
+
 class _FFNCore(torch.autograd.Function):
     """y = dropout(gelu(x W1^T + b1)) W2^T (+ b2) on bf16 operands; see the module docstring.
     ``out_bias_grad=False``: b2's gradient is left to the consumer of y (ops/dropout.py
@@ -72,12 +112,16 @@ class _FFNCore(torch.autograd.Function):
         shp = x.shape
         x2 = x.reshape(-1, shp[-1]).to(dt).contiguous()
         w1c, w2c = cast_weight(w1, dt).contiguous(), cast_weight(w2, dt).contiguous()
-        b1f = b1.detach().float().contiguous()
         M, d_ff = x2.shape[0], w1.shape[0]
         seed, sptr = _seed(p)
-        if SIDES in ("both", "fwd"):
+        if SIDES in ("both", "fwd") and KERNEL == "gemm":
             a = torch.empty(M, d_ff, device=x.device, dtype=dt)
             h = torch.empty_like(a)
+            _gemm_gelu(x2, w1c, 0, a, h, bias=cast_weight(b1, dt).detach().contiguous(), p=p, seed=seed, sptr=sptr)
+        elif SIDES in ("both", "fwd"):
+            a = torch.empty(M, d_ff, device=x.device, dtype=dt)
+            h = torch.empty_like(a)
+            b1f = b1.detach().float().contiguous()
             _gemm(x2, w1c, a, EPI_GELU_FWD, bias=b1f, out2=h, p=p, seed=seed, sptr=sptr, tile=TILE_FWD)
         else:  # library GEMM + the standalone GELU-dropout pass (same mask: same seed, same hash)
             a = F.linear(x2, w1c, cast_weight(b1, dt))
@@ -107,7 +151,15 @@ class _FFNCore(torch.autograd.Function):
                 dw2 = wgrad(g2, h).to(w2.dtype)
         if b2 is not None and ctx.needs_input_grad[4] and out_bias_grad:
             tgt = direct_target(b2)
-            if tgt is not None:
+            if KERNEL == "gemm":  # row-block sums folded in order: repeatable, like b1's below
+                db2 = tgt if tgt is not None else torch.zeros(g2.shape[1], device=g2.device, dtype=torch.float32)
+                _colsum_into(g2, db2.view(-1))
+                if tgt is not None:
+                    mark_ready(b2)
+                    db2 = None
+                else:
+                    db2 = db2.to(b2.dtype)
+            elif tgt is not None:
                 bias_grad_into(g2, tgt)
                 mark_ready(b2)
             else:
@@ -116,7 +168,12 @@ class _FFNCore(torch.autograd.Function):
         ga = torch.empty_like(a)
         tb1 = direct_target(b1) if ctx.needs_input_grad[2] else None
         gb = tb1 if tb1 is not None else torch.zeros(a.shape[1], device=a.device, dtype=torch.float32)
-        if SIDES in ("both", "bwd"):
+        if SIDES in ("both", "bwd") and KERNEL == "gemm":
+            # W_2 as stored; the per-panel column sums folded in panel order: gb += sum over panels
+            gbslab = torch.empty((a.shape[0] + 127) // 128, a.shape[1], device=a.device, dtype=torch.float32)
+            _gemm_gelu(g2, w2c, 1, a, ga, gbslab=gbslab, p=p, seed=seed, sptr=sptr)
+            bias_fold_into(gbslab, gb.view(-1))
+        elif SIDES in ("both", "bwd"):
             w2t = w2c.t().contiguous()  # [d_ff][d_model]: the kernel's K-contiguous weight operand
             _gemm(g2, w2t, ga, EPI_GELU_BWD, a_in=a, gb=gb, p=p, seed=seed, sptr=sptr, tile=TILE_BWD)
         else:
