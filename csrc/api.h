@@ -212,6 +212,13 @@ void attn_fwd(uint64_t q, uint64_t k, uint64_t v, const std::vector<long>& strid
 void attn_bwd(uint64_t q, uint64_t k, uint64_t v, const std::vector<long>& strides, uint64_t o32, uint64_t dout,
               uint64_t lse, uint64_t delta, uint64_t mask, uint64_t dq, uint64_t dk, uint64_t dv, int B, int L, int H,
               float fill, float p_drop, uint64_t seed, uint64_t seed_ptr, long grad_ld, uint64_t stream);
+// attention_varlen.hip: qkv [T][3][H][64] packed sequences, cu_seqlens [B+1] int32 on the device
+void attn_varlen_fwd(uint64_t qkv, long qkv_ld, uint64_t cu_seqlens, uint64_t out, uint64_t out32, uint64_t lse,
+                     int B, int T, int H, int max_len, float p_drop, uint64_t seed, uint64_t seed_ptr,
+                     uint64_t stream);
+void attn_varlen_bwd(uint64_t qkv, long qkv_ld, uint64_t cu_seqlens, uint64_t o32, uint64_t dout, uint64_t lse,
+                     uint64_t delta, uint64_t dqkv, long grad_ld, int B, int T, int H, int max_len, float p_drop,
+                     uint64_t seed, uint64_t seed_ptr, uint64_t stream);
 // dropout.hip
 void dropout_add_fwd(uint64_t y, uint64_t x, uint64_t out, long n, float p, uint64_t seed, uint64_t seed_ptr,
                      uint64_t stream);

@@ -33,17 +33,11 @@
 // mask; the reference's -1e-9 fill, survey Q7, is reproduced with fill = -1e-9).  Dropout:
 // a counter-based hash of (seed, b, h, q, key) -- the same keep mask in all kernels, no
 // mask tensor.
-#include "common.h"
+#include "attention_mma.h"  // fragment types, ld8 / ldtr / pack8 / mfma / crow, kD, kRowLd, drop_hash
 
 namespace fdt {
 namespace attn {
 
-typedef short bf16x8_t __attribute__((ext_vector_type(8)));
-typedef short bf16x4_t __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-constexpr int kD = 64;
-constexpr int kRowLd = kD + 8;  // [row][d] images: 144-B rows -> ds_read_b128 of 16 rows hits 64 distinct banks
 constexpr int kBlk = 128;       // queries (fwd, dq) / keys (dkdv) per workgroup: 4 waves x 32
 constexpr int kTile = 64;       // keys (fwd, dq) / queries (dkdv) staged per loop iteration
 
@@ -80,47 +74,8 @@ struct Args {
 // 32-bit multiplies; the 64-bit mix it replaces cost ~3x the VALU work per score element)
 // (lin = (bh L + q) L + key: the callers form it with adds from per-lane / per-tile bases)
 __device__ __forceinline__ bool dropped_lin(const Args& a, uint32_t lin) {
-  uint32_t x = lin ^ (uint32_t)a.seed;
-  x += (uint32_t)(a.seed >> 32);
-  x ^= x >> 16;
-  x *= 0x85ebca6bu;
-  x ^= x >> 13;
-  x *= 0xc2b2ae35u;
-  x ^= x >> 16;
-  return x < a.drop_thr;
+  return drop_hash(a.seed, lin) < a.drop_thr;
 }
-
-// raw v_exp_f32 (exp2f adds a compare / select / ldexp per call for denormal results, which
-// probabilities below 2^-126 do not need); exp2(-inf) = 0
-__device__ __forceinline__ float fexp2(float x) { return __builtin_amdgcn_exp2f(x); }
-
-__device__ __forceinline__ bf16x8_t ld8(const bf16* p) { return *reinterpret_cast<const bf16x8_t*>(p); }
-
-typedef __attribute__((address_space(3))) bf16x4_t lds_bf16x4;
-
-// Transposed MFMA fragment straight from a ROW image [row][kRowLd] (gfx950 ds_read_b64_tr_b16,
-// no transposed LDS copy): lane l gets column c0 + (l & 31) and the k elements = rows
-// R..R+3 (lo) and R+8..R+11 (hi), R = r0 + 4h -- the permuted order of the accumulator rows.
-// In each 16-lane group lane 4q+p supplies row R+q, columns 16g + 4p..4p+3 (g = (l >> 4) & 1).
-__device__ __forceinline__ bf16x8_t ldtr(const bf16* img, int r0, int c0, int lane) {
-  const int q = (lane & 15) >> 2, p = lane & 3, g = (lane >> 4) & 1, h = lane >> 5;
-  const bf16* p0 = img + (r0 + 4 * h + q) * kRowLd + c0 + 16 * g + 4 * p;
-  const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(p0));
-  const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4*)(p0 + 8 * kRowLd));
-  return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
-}
-
-__device__ __forceinline__ bf16x8_t pack8(const float* v) {
-  const uint4 u = make_uint4(pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]),
-                             pack_bf16x2(v[6], v[7]));
-  return __builtin_bit_cast(bf16x8_t, u);
-}
-
-__device__ __forceinline__ f32x16 mfma(bf16x8_t a, bf16x8_t b, f32x16 c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
-}
-
-__device__ __forceinline__ int crow(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h; }
 
 // rows [r0, r0 + 64) of a strided [L][64] matrix -> row image [64][kRowLd] (16-B stores;
 // transposed operands are read from it with ldtr); rows past L are zero.

@@ -29,7 +29,7 @@ import torch.nn.functional as F
 
 from ..ops import ffn
 from ..ops.dropout import dropout_add, gelu_dropout
-from ..ops.attention import packed_attention, scaled_dot_product_attention
+from ..ops.attention import packed_attention, scaled_dot_product_attention, varlen_attention
 from ..ops.embedding import embedding_sum
 from ..ops.layernorm import ResidualGrad, layer_norm_unbiased
 from ..ops.linear import linear, linear_cat
@@ -92,9 +92,17 @@ class Transformer(nn.Module):
             return float(torch.distributions.beta.Beta(self.alpha, self.alpha).sample())
         return float(self.alpha)
 
-    def forward(self, x, token_types, index, mask=None):
+    def forward(self, x, token_types, index, mask=None, cu_seqlens=None, max_len=None):
         """Returns ``(logits, perm_index, lam)`` like the reference (``transformer.py:84``).
-        ``mask`` is the ``(B,1,1,L)`` attention mask (1 = keep)."""
+        ``mask`` is the ``(B,1,1,L)`` attention mask (1 = keep).
+
+        Packed batch (``pack_tokens``): with ``cu_seqlens`` (B + 1 row offsets on the device) and
+        ``max_len``, ``x`` and ``token_types`` are ``[1, T]`` streams of the real tokens and
+        ``mask`` must be None.  Every token-wise op runs on the T rows only; attention keeps
+        the sequences apart (``ops.attention.varlen_attention``), and the pooler reads the first
+        row of each sequence.  Nothing here reads ``cu_seqlens`` on the host."""
+        if cu_seqlens is not None:
+            return self._forward_packed(x, token_types, index, mask, cu_seqlens, max_len)
         embeddings = self.input_embeddings(x, token_types, index)
         encodings = self.input_encodings(embeddings)
         x = embeddings + encodings
@@ -106,7 +114,30 @@ class Transformer(nn.Module):
         for i in range(self.n_layers):
             x = self.sublayer_attention[i](x, mask)
             x = self.sublayer_ffn[i](x)
-        x = self.pooler(x)
+        return self._head(self.pooler(x))
+
+    def _forward_packed(self, x, token_types, index, mask, cu_seqlens, max_len):
+        if self.faithful:
+            raise ValueError("faithful=True lets padding be attended (-1e-9 fill); a packed batch has no padding")
+        if mask is not None or max_len is None or x.dim() != 2 or x.size(0) != 1:
+            raise ValueError("packed forward: x and token_types are [1, T], mask is None, max_len is given")
+        T, n_seq = x.size(1), cu_seqlens.numel() - 1
+        # sequence id and in-sequence position of every row: static shapes, on the device
+        rows = torch.arange(T, device=x.device)
+        cu = cu_seqlens.to(torch.long)
+        seq = torch.searchsorted(cu[1:].contiguous(), rows, right=True).clamp_(max=n_seq - 1)
+        pos = (rows - cu[seq]).clamp_(0, self.input_embeddings.maxlen - 1)
+        embeddings = self.input_embeddings(x, token_types, index, pos)
+        encodings = self.input_encodings(embeddings, pos)
+        x = embeddings + encodings
+        if cu_seqlens.dtype != torch.int32:
+            cu_seqlens = cu_seqlens.to(torch.int32)  # once per forward (the kernels take int32)
+        for i in range(self.n_layers):
+            x = self.sublayer_attention[i](x, None, cu_seqlens, int(max_len))
+            x = self.sublayer_ffn[i](x)
+        return self._head(self.pooler(x, cu[:-1].clamp(max=T - 1)))
+
+    def _head(self, x):
         x = self.dropout_post(x)
         b = x.size(0)
         mix = self.training or self.faithful
@@ -136,7 +167,10 @@ class Pooler(nn.Module):
         super().__init__()
         self.dense = nn.Linear(hidden_size, hidden_size)
 
-    def forward(self, x):
+    def forward(self, x, first_rows=None):
+        """``first_rows``: packed stream [1, T, d], the row of token 0 of every sequence."""
+        if first_rows is not None:
+            return torch.tanh(self.dense(x[0].index_select(0, first_rows)))
         return torch.tanh(self.dense(x[:, 0, :]))
 
 
@@ -163,7 +197,10 @@ class PositionalEncoding(nn.Module):
             self._pe_cache[key] = t
         return t
 
-    def forward(self, x):
+    def forward(self, x, pos=None):
+        """``pos``: packed stream, the in-sequence position of every row (gathers the table)."""
+        if pos is not None:
+            return self.dropout(x + self.table(x.device, x.dtype)[0].index_select(0, pos).unsqueeze(0))
         return self.dropout(x + self.table(x.device, x.dtype)[:, :x.size(1)])
 
 
@@ -180,9 +217,12 @@ class Embeddings(nn.Module):
         self.d_model = d_model
         self.maxlen = maxlen
 
-    def forward(self, x, token_types, index):
+    def forward(self, x, token_types, index, pos=None):
         L = x.size(1)
-        pos_ids = index[:L] if index is not None else torch.arange(L, device=x.device)
+        if pos is not None:  # packed stream: one position per row
+            pos_ids = index[pos] if index is not None else pos
+        else:
+            pos_ids = index[:L] if index is not None else torch.arange(L, device=x.device)
         return embedding_sum(x, token_types, pos_ids, self.token_embedding.weight,
                              self.pos_embedding.weight, self.segment_embedding.weight,
                              math.sqrt(self.d_model))
@@ -224,10 +264,18 @@ class MultiheadAttention(nn.Module):
         self.faithful = faithful
         self.attn = None
 
-    def forward(self, query, key, value, mask=None, fuse_out_bias=False):
+    def forward(self, query, key, value, mask=None, fuse_out_bias=False, cu_seqlens=None, max_len=None):
         """``fuse_out_bias``: the caller's dropout_add computes the output projection's bias
-        gradient (ops/dropout.py ``bias=``)."""
+        gradient (ops/dropout.py ``bias=``).  ``cu_seqlens``, ``max_len``: self-attention over a
+        packed [1, T, d] stream of sequences."""
         b, L, _ = query.shape
+        if cu_seqlens is not None:
+            assert query is key and key is value and b == 1 and mask is None
+            qkv = linear_cat(query, [l.weight for l in self.heads], [l.bias for l in self.heads])
+            p = self.dropout.p if self.training else 0.0
+            x = varlen_attention(qkv.view(L, 3, self.h, self.d_k), cu_seqlens, max_len, dropout_p=p)
+            return linear(x.reshape(1, L, self.h * self.d_k), self.output.weight, self.output.bias,
+                          bias_grad=not fuse_out_bias)
         if query is key and key is value:
             qkv = linear_cat(query, [l.weight for l in self.heads], [l.bias for l in self.heads])
             qkv = qkv.view(b, L, 3, self.h, self.d_k)
@@ -263,10 +311,10 @@ class sublayerConnectionAttention(nn.Module):  # noqa: N801 (reference name)
         self.layernorm = LayerNorm(d_model)
         self.dropout = nn.Dropout(p=dropout_connection)
 
-    def forward(self, x, mask=None):
+    def forward(self, x, mask=None, cu_seqlens=None, max_len=None):
         res = ResidualGrad()  # skip gradient handed to the LayerNorm backward (no add pass)
         y = self.layernorm(x, res)
-        y = self.multiheads(y, y, y, mask, fuse_out_bias=True)
+        y = self.multiheads(y, y, y, mask, fuse_out_bias=True, cu_seqlens=cu_seqlens, max_len=max_len)
         return dropout_add(y, x, self.dropout.p, self.training, res, bias=self.multiheads.output.bias)
 
 
@@ -318,3 +366,22 @@ class FusedMLP(nn.Module):
             nn.init.constant_(self.b1, 0.0)
         if self.b2 is not None:
             nn.init.constant_(self.b2, 0.0)
+
+
+def pack_tokens(ids, token_types, lengths, multiple=1):
+    """A padded ``(B, L)`` batch plus its lengths -> ``(ids[1, T], types[1, T], cu_seqlens,
+    max_len)`` for the packed forward: the real tokens back to back, T rounded up to
+    ``multiple`` (slack positions take id 0 and type 0), ``cu_seqlens`` int32 ``[B + 1]`` on the
+    batch's device, ``max_len`` the longest length (a host int).  Runs on the host side of the
+    step and may synchronise."""
+    lengths = torch.as_tensor(lengths, dtype=torch.long, device="cpu").clamp(0, ids.size(1))
+    total = int(lengths.sum())
+    T = max(-(-max(total, 1) // multiple) * multiple, 1)
+    keep = (torch.arange(ids.size(1))[None, :] < lengths[:, None]).to(ids.device)
+    out_ids = ids.new_zeros(1, T)
+    out_types = token_types.new_zeros(1, T)
+    out_ids[0, :total] = ids[keep]
+    out_types[0, :total] = token_types[:, :ids.size(1)][keep]
+    cu = torch.zeros(lengths.numel() + 1, dtype=torch.int32)
+    cu[1:] = lengths.cumsum(0)
+    return out_ids, out_types, cu.to(ids.device), max(int(lengths.max()), 1)

@@ -51,6 +51,36 @@ def scaled_dot_product_attention(q, k, v, mask=None, dropout_p=0.0, mask_value=N
     return attention_reference(q, k, v, mask, dropout_p, mask_value)
 
 
+def varlen_attention_reference(qkv, cu_seqlens, max_len, dropout_p=0.0):
+    """The packed operation one sequence at a time through ``attention_reference`` (reads
+    ``cu_seqlens`` on the host: the CPU and fp32 oracle path).  Slack rows are zero."""
+    T, _, H, D = qkv.shape
+    cu = [int(c) for c in cu_seqlens.tolist()]
+    pieces, row = [], 0
+    for s0, s1 in zip(cu[:-1], cu[1:]):
+        n = min(s1 - s0, int(max_len))
+        if n > 0:
+            q, k, v = qkv[s0:s0 + n].unsqueeze(0).unbind(2)
+            pieces.append(attention_reference(q, k, v, None, dropout_p)[0])
+        pieces.append(qkv.new_zeros(s1 - s0 - n, H, D))
+        row = s1
+    pieces.append(qkv.new_zeros(T - row, H, D))
+    return torch.cat(pieces, 0)
+
+
+def varlen_attention(qkv, cu_seqlens, max_len, dropout_p=0.0):
+    """Attention over a packed stream of sequences with no padding.  qkv: (T, 3, H, D), the fused
+    Q/K/V projection of the packed tokens; cu_seqlens: (B + 1,) row offsets (cu[0] = 0,
+    non-decreasing, cu[B] <= T); max_len: an upper bound on every sequence length.  Returns
+    (T, H, D); rows past cu[B] are zero.  On MI355X bf16 with head dim 64 runs the HIP kernels
+    of ``csrc/kernels/attention_varlen.hip``, which never read ``cu_seqlens`` on the host."""
+    if _native.use_native(qkv):
+        from . import attention_native as an
+        if an.varlen_supported(qkv, cu_seqlens):
+            return an.attention_varlen_packed(qkv, cu_seqlens, max_len, dropout_p)
+    return varlen_attention_reference(qkv, cu_seqlens, max_len, dropout_p)
+
+
 def packed_attention(qkv, mask=None, dropout_p=0.0, mask_value=None):
     """qkv: (B, L, 3, H, D), the fused Q/K/V projection output.  On MI355X the HIP kernels
     read Q/K/V in place and write the packed gradient; otherwise unbind + the reference."""

@@ -96,6 +96,61 @@ class FlashAttention(torch.autograd.Function):
         return dq, dk, dv, None, None, None
 
 
+class VarlenAttention(torch.autograd.Function):
+    """Packed variable-length attention (``csrc/kernels/attention_varlen.hip``): qkv is the
+    fused projection [T, 3, H, 64] of a packed token stream, ``cu_seqlens`` [B + 1] int32 stays
+    on the device (never read here), ``max_len`` bounds every sequence.  The gradient is written
+    as one packed [T, 3, H, 64] tensor; lse and delta are fp32 [H, T]."""
+
+    @staticmethod
+    def forward(ctx, qkv, cu_seqlens, max_len: int, dropout_p: float):
+        nat = _native.native()
+        T, three, H, D = qkv.shape
+        assert three == 3 and D == HEAD_DIM and qkv.stride(3) == 1 and qkv.stride(2) == D and qkv.stride(1) == H * D
+        assert cu_seqlens.dtype == torch.int32 and cu_seqlens.is_cuda and cu_seqlens.is_contiguous()
+        B = cu_seqlens.numel() - 1
+        out = torch.empty(T, H, D, device=qkv.device, dtype=torch.bfloat16)
+        lse = torch.empty(H, T, device=qkv.device, dtype=torch.float32)
+        out32 = torch.empty(T, H, D, device=qkv.device, dtype=torch.float32) if ctx.needs_input_grad[0] else None
+        seed = int(torch.randint(0, 2**62, (1,)).item()) if dropout_p > 0 else 0
+        sptr = DEVICE_SEED.data_ptr() if (DEVICE_SEED is not None and dropout_p > 0) else 0
+        nat.attn_varlen_fwd(qkv.data_ptr(), qkv.stride(0), cu_seqlens.data_ptr(), out.data_ptr(),
+                            0 if out32 is None else out32.data_ptr(), lse.data_ptr(), B, T, H, int(max_len),
+                            float(dropout_p), seed, sptr, _native.stream_ptr())
+        ctx.save_for_backward(qkv, out32, lse, cu_seqlens)
+        ctx.cfg = (int(max_len), float(dropout_p), seed, sptr)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        nat = _native.native()
+        qkv, out32, lse, cu_seqlens = ctx.saved_tensors
+        max_len, p, seed, sptr = ctx.cfg
+        T, _, H, D = qkv.shape
+        g = g.contiguous().to(torch.bfloat16)
+        dqkv = torch.empty(T, 3, H, D, device=qkv.device, dtype=torch.bfloat16)
+        delta = torch.empty(H, T, device=qkv.device, dtype=torch.float32)
+        nat.attn_varlen_bwd(qkv.data_ptr(), qkv.stride(0), cu_seqlens.data_ptr(), out32.data_ptr(), g.data_ptr(),
+                            lse.data_ptr(), delta.data_ptr(), dqkv.data_ptr(), dqkv.stride(0),
+                            cu_seqlens.numel() - 1, T, H, max_len, p, seed, sptr, _native.stream_ptr())
+        return dqkv, None, None, None
+
+
+def varlen_supported(qkv, cu_seqlens) -> bool:
+    return (qkv.is_cuda and qkv.dtype == torch.bfloat16 and qkv.dim() == 4 and qkv.shape[1] == 3
+            and qkv.shape[3] == HEAD_DIM and qkv.stride(3) == 1 and qkv.stride(2) == HEAD_DIM
+            and qkv.stride(1) == qkv.shape[2] * HEAD_DIM and qkv.stride(0) % 8 == 0 and cu_seqlens.is_cuda)
+
+
+def attention_varlen_packed(qkv, cu_seqlens, max_len, dropout_p=0.0):
+    """qkv: (T, 3, H, 64) bf16 packed sequences; cu_seqlens: (B + 1,) device int32 row offsets
+    (cu[0] = 0, non-decreasing, cu[B] <= T); returns (T, H, 64) bf16.  Rows past cu[B] and the
+    rows of a sequence past ``max_len`` come back exactly zero, as do their gradients."""
+    if cu_seqlens.dtype != torch.int32 or not cu_seqlens.is_contiguous():
+        cu_seqlens = cu_seqlens.to(torch.int32).contiguous()
+    return VarlenAttention.apply(qkv, cu_seqlens, int(max_len), float(dropout_p))
+
+
 def _mask_u8(mask):
     if mask is None:
         return None
